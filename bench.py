@@ -15,6 +15,13 @@ images per step.  ``value`` = images processed by all ranks ÷ the max-over-rank
 Launch: ``python bench.py`` (1 GPU), ``python bench.py --gpus N`` (starts N ranks itself, one per
 GPU, RCCL), or ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1
 bench.py --gpus N`` (the launcher's WORLD_SIZE must equal N).  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs: set-up, ``--warmup`` steps, ``--steps`` timed
+steps (``ms_per_step`` = the timed region ÷ ``--steps``), the line.  The per-kernel figures in it
+come from HIP events recorded inside those timed steps.  ``--full`` adds the measurements that
+take runs of their own (the CPU baseline, the selection launches timed in isolation, the eager
+pass behind ``--graph 1``'s per-kernel times); ``--dump-outputs DIR`` writes the last timed
+step's outputs as ``DIR/<name>.npy`` so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -395,6 +402,47 @@ def cpu_baseline(args, legs_only=False):
                       f"value_N10 = the same at N=10 tokens ({dt10:.1f} s)"}
 
 
+# ------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _named_arrays(name, obj, out):
+    """Flatten what a step returned (tensors, numbers, and tuples / lists / dicts of them) into
+    out[name] = numpy array; None entries are left out."""
+    if obj is None:
+        return
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            _named_arrays(f"{name}_{k}" if name else str(k), v, out)
+    elif isinstance(obj, (list, tuple)):
+        if obj and all(torch.is_tensor(t) and t.shape == obj[0].shape for t in obj):
+            out[name] = torch.stack([t.detach() for t in obj]).cpu().numpy()
+        else:
+            for i, v in enumerate(obj):
+                _named_arrays(f"{name}_{i}", v, out)
+    elif torch.is_tensor(obj):
+        out[name] = obj.detach().cpu().numpy()
+    else:
+        out[name] = np.asarray(obj)
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs DIR: DIR/<name>.npy for every output of the last timed step, float32 (float64
+    for float64 and integer outputs, which float32 cannot hold exactly), at most DUMP_LIMIT_BYTES
+    in all: an output larger than its equal share of the limit is stored as a fixed, seeded sample
+    of its flattened elements (the same elements in every run)."""
+    arrays = {}
+    _named_arrays("", outputs, arrays)
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, order="C", dtype=np.float32 if a.dtype in (np.float32, np.float16) else np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------ GPU bench
 def _tuned_gemms_in_use():
     from stablekeypoints_amd.tuning import _state
@@ -462,6 +510,9 @@ def stage_main(args, ldm, controllers, context, dev, world, rank, backend):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"indices": out} if args.stage == "find_indices" else
+                     dict(zip(("source_keypoints", "target_keypoints", "visibility"), out)))
     # find_indices shards the images over the ranks (weak); tta splits each image's augmentations
     # over the ranks (the reference's augmentation_iterations // num_gpus per replica: strong)
     images = (world * n if args.stage == "find_indices" else n) * args.steps
@@ -538,7 +589,19 @@ def main():
     ap.add_argument("--tokens", type=int, default=500)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--upsample-res", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, each in runs of its own outside the "
+                         "timed steps: the CPU baseline (unless --no-cpu-baseline), the selection launches timed "
+                         "apart in isolation (kernels.a8_split_isolated) and, with --graph 1, the eager pass that "
+                         "gives the per-kernel times.  Off by default: a plain run sets up, warms up, times "
+                         "--steps steps and prints the line (cpu_baseline null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all): token_opt: the embedding after the step's Adam "
+                         "update, the step's three running losses and the token rows it selected per image; "
+                         "find_indices: the ranked token indices; tta: the keypoints (and visibility).  The "
+                         "inputs are seeded: the same arguments give the same inputs in every run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--conv-benchmark", type=int, default=0, help="torch.backends.cudnn.benchmark (MIOpen exhaustive find)")
     ap.add_argument("--conv", default="wino", choices=["wino", "miopen"],
                     help="3x3 stride-1 convolutions: skp_conv3x3_wino where eligible, or MIOpen throughout")
@@ -578,6 +641,8 @@ def main():
     args = ap.parse_args()
     if args.cpu_leg:
         return cpu_leg_main(args)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.graph and args.prefetch < 1:
         args.prefetch = 1   # only prefetched passes replay a graph (TokenOptimizer.micro_steps)
 
@@ -645,8 +710,9 @@ def main():
     ops.set_kernel_timer(timer)
 
     counter = [0]
+    selected = [None] * args.accum   # the token rows micro_steps returned for each image of the last step
 
-    mb = args.micro_batch if args.micro_batch > 0 else args.accum
+    mb =args.micro_batch if args.micro_batch > 0 else args.accum
 
     def batch_at(c, n):
         return [imgs[(c + i) % len(imgs)] for i in range(n)]
@@ -661,7 +727,8 @@ def main():
                 opt.prefetch(cur)                                   # no-op when already prefetched
                 ahead = [batch_at(counter[0] + d * n, min(mb, args.accum)) for d in range(1, args.prefetch + 1)]
             # the next passes' VAE is enqueued between this pass's forward and backward
-            opt.micro_steps(cur, prefetch=ahead)
+            sel = opt.micro_steps(cur, prefetch=ahead)
+            selected[done:done + n] = sel                           # per image: its selected token rows
             counter[0] += n
             done += n
         return opt.optimizer_step()
@@ -671,9 +738,9 @@ def main():
             import torch.distributed as dist
             dist.barrier()
 
-    # the A8 call's launches timed apart in isolation, before the warm-up (kept out of the traces'
-    # timed region)
-    a8_split = _a8_split(dev, args.tokens, args.upsample_res) if args.model == "sd15" else None
+    # --full: the A8 call's launches timed apart in isolation, before the warm-up (kept out of the
+    # traces' timed region; its generator is its own, so the steps draw the same noise either way)
+    a8_split = _a8_split(dev, args.tokens, args.upsample_res) if args.full and args.model == "sd15" else None
     for _ in range(args.warmup):
         step()
     barrier()
@@ -695,12 +762,14 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"context": opt.context, "selected_tokens": selected, **rec})
     images = world * args.accum * args.steps
     value = images / elapsed
     timing_src = ("HIP events around every launch in the timed region, on the launching stream "
                   "(bench.py KernelTimer); launches that overlap the side-stream VAE prefetch share the GPU "
                   "with it (isolated launch times: tools/kbench.py)")
-    if args.graph:
+    if args.graph and args.full:
         # the timed steps replay a HIP graph, which runs no Python and so records no per-kernel
         # events: the same pass runs once eagerly after the timed region (same shapes, same
         # kernels) with the events around every libskp launch
@@ -800,7 +869,7 @@ def main():
                         "GB/s_algorithmic": s_["bytes_per_launch"] / (s_["avg_ms"] * 1e-3) / 1e9}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "sd15":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "sd15":
         ops.set_kernel_timer(None)
         cpu = cpu_baseline(args)
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A round's evidence refresh on the committed tree, part PART (default "bench"):
-#   bench: smoke, the default bench (with cpu_baseline), STAGE_RUNS (default 3) runs each of the
+#   bench: smoke, the default bench with --full (cpu_baseline, isolated selection), STAGE_RUNS (default 3) runs each of the
 #          eval-stage benches, rocprofv3 kernel traces of the token-opt bench and both stages,
 #          timed-region summaries; DIST=1: bench.py --gpus 2 on one GPU (gloo); SDXL=1: configs[4]
 #   suite: the whole -m gpu suite (-s: the parity prints), then the PMC passes (tools/gpu_pmc.sh)
@@ -15,7 +15,7 @@ cd $ROOT
 if [ "${PART:-bench}" = "bench" ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 3; }
   grep -v amdgpu $O/smoke.log | tail -3
-  timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1 || { echo "bench failed rc=$?"; tail -30 $O/bench.log; exit 4; }
+  timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1 || { echo "bench failed rc=$?"; tail -30 $O/bench.log; exit 4; }
   tail -1 $O/bench.log | cut -c1-300
   for i in $(seq 1 ${STAGE_RUNS:-3}); do
     timeout -k 10 300 python -u bench.py --stage find_indices --tokens 100 --steps 3 --warmup 1 > $O/bench_find_100_$i.log 2>&1 || { echo "find_indices failed rc=$?"; tail -30 $O/bench_find_100_$i.log; exit 5; }
