@@ -396,6 +396,35 @@ int skp_conv3x3_wino2_gn(const float* x, const float* U, const float* bias, cons
 int skp_conv3x3s2_wino2(const float* x, const float* U, const float* bias, float* y, int B, int C, int K, int H,
                         int W, int nsplit, float* ws, void* stream);
 
+/* ---------------------------------------------------------------- A17 visualisation sheets
+ * Per-map (min, max) for the heat overlay: the normalisation of visualize.py:60-61
+ * (save_grid: map − min, then / max).  maps (n, h, w) -> range (n, 2).  A map that holds a NaN
+ * or ±inf, or whose max equals its min, gets (NaN, NaN), which the sheet reads as "no
+ * overlay".  16-B loads when h·w % 4 == 0 and maps is 16-B aligned, scalar loads otherwise;
+ * bit-exact (min/max do not depend on the order).                                          */
+int skp_map_range(const float* maps, int n, int h, int w, float* range, void* stream);
+/* One uint8 RGB sheet of rows × cols tiles, replacing the matplotlib figures of
+ * visualize.py:105-138 (plot_point_correspondences: images with one marker per keypoint) and
+ * visualize.py:40-73 (save_grid: images under the normalised map at alpha 0.7).
+ *   images (n, 3, H, W) in [0, 1]; maps (n, h, w) or NULL; range (n, 2) from skp_map_range;
+ *   lut (256, 3) in [0, 1]; points (n, K, 2) normalised (row, col) or NULL / K == 0;
+ *   colors (K, 3) uint8; out (rows·(th+pad)+pad, cols·(tw+pad)+pad, 3) uint8, th = H/f,
+ *   tw = W/f.  Tile t (row-major) shows image t; tiles t >= n and all padding are 255.
+ * Output pixel (y, x) of tile t, in fp32: the mean over its f×f source pixels of
+ * comp = img (no map, or range[t] NaN) or (1−alpha)·img + alpha·LUT(v),
+ * v = clamp((m − mn)/(mx − mn), 0, 1), m = the map sampled bilinearly (align_corners=False, as
+ * skp_resize_bilinear) at the source pixel, LUT(v) linear between entries floor(255v) and the
+ * next; byte = floor(clamp(c, 0, 1)·255 + 0.5).  Then markers j = 0 … K−1 in order (the last
+ * wins) with centre (py·th, px·tw): d² = (y+0.5−py·th)² + (x+0.5−px·tw)² <= radius² paints
+ * colors[j], else d² <= (radius+1)² paints white; a NaN coordinate paints nothing; a marker
+ * never leaves its tile.  A gather (one thread per output pixel, no atomics): deterministic.
+ * Rejected: H % f or W % f != 0, n > rows·cols, maps without range or lut, K > 64, a sheet
+ * of 2^31 bytes or more.                                                                   */
+int skp_render_sheet(const float* images, int n, int H, int W, const float* maps, int h, int w, const float* range,
+                     const float* lut, float alpha, const float* points, int K, float radius,
+                     const unsigned char* colors, int rows, int cols, int f, int pad, unsigned char* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

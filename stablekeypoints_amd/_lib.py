@@ -90,6 +90,9 @@ _SIGS = {
     "skp_groupnorm_fwd_part": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_ll, _c_int, _c_float, _c_int, _p, _p, _p,
                                _p],
     "skp_conv3x3s2_wino2": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p],
+    "skp_map_range": [_p, _c_int, _c_int, _c_int, _p, _p],
+    "skp_render_sheet": [_p, _c_int, _c_int, _c_int, _p, _c_int, _c_int, _p, _p, _c_float, _p, _c_int, _c_float, _p,
+                         _c_int, _c_int, _c_int, _c_int, _p, _p],
     "skp_version": [],
 }
 

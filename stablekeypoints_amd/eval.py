@@ -7,6 +7,7 @@ reference's semantics (first-occurrence argmax, NaN is max, in-place mutation in
 test-time-augmentation average on the same kernels; ``evaluate`` (``:374-539``) regresses
 keypoints from it and scores them with the reference's five metrics (``keypoint_error``).
 """
+import contextlib
 import os
 
 import torch
@@ -33,6 +34,21 @@ def mask_radius(map, max_coords, radius):
 def pixel_from_weighted_avg(heatmaps, distance=5):
     """eval.py:113-155 (zeros pixels beyond ``distance`` IN PLACE, like the reference)."""
     return ops.pixel_from_weighted_avg(heatmaps, distance=distance)
+
+
+@contextlib.contextmanager
+def _reproducible_convolutions():
+    """MIOpen restricted to its deterministic solvers while the TTA captures run.  The library's
+    default choice for the VAE encoder's stride-2 3×3 convolution at 128² sums in a run-dependent
+    order (first seen there: two same-seed TTA calls differed by 2e-8 … 4.5e-8 on map values of
+    3e-2), so maps written by one run (``create_vid``'s ``saved_maps.pt``) could not be
+    reproduced bit for bit by the next.  The training path does not pass through here."""
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.deterministic = was
 
 
 # default TTA batch bound: warped copies per capture pass × pixels per copy (10 copies at 512², the
@@ -98,15 +114,16 @@ def run_image_with_context_augmented(ldm, image, context, indices, device="cuda"
         if world > 1:
             theta = theta.reshape(c, num_gpus, 2, 3)[:, rank]
         aug = T(img[None].expand(theta.shape[0], -1, -1, -1), theta=theta)
-        if aug.shape[0] == 1:
-            maps = torch.stack(ptp_utils.run_and_find_attn(
-                ldm, aug, context, layers=layers, noise_level=noise_level, from_where=from_where,
-                upsample_res=upscale_size, device=device, controllers=controllers, indices=indices))
-        else:
-            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
-                                                        layers=layers, upsample_res=upscale_size, indices=indices,
-                                                        controllers=controllers)
-            maps = torch.stack([per[k][b] for b in range(aug.shape[0]) for k in range(len(per))])
+        with _reproducible_convolutions():
+            if aug.shape[0] == 1:
+                maps = torch.stack(ptp_utils.run_and_find_attn(
+                    ldm, aug, context, layers=layers, noise_level=noise_level, from_where=from_where,
+                    upsample_res=upscale_size, device=device, controllers=controllers, indices=indices))
+            else:
+                per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level,
+                                                            device=device, layers=layers, upsample_res=upscale_size,
+                                                            indices=indices, controllers=controllers)
+                maps = torch.stack([per[k][b] for b in range(aug.shape[0]) for k in range(len(per))])
         num_samples += T.inverse(torch.ones_like(maps)).sum(dim=0)
         sum_samples += T.inverse(maps).sum(dim=0)
         done += c

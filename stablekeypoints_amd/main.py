@@ -3,9 +3,11 @@
 optimize (``optimize_embedding`` → ``embedding.pt``) → find_indices (``find_best_indices`` →
 ``indices.pt``) → precompute (``precompute_all_keypoints`` → ``source_keypoints.pt``,
 ``target_keypoints.pt``, ``visible.pt``) → regressor (``regressor.pt``) → evaluate
-(``all_errors.pt``).  ``--start_from_stage`` resumes from the saved files.  Visualisation
-(``visualize_attn_maps``) is not built.  Multi-GPU: like the reference, one command uses every
-visible GPU — it starts one rank per GPU under ``torch.distributed.run`` (``--num_gpus`` to pick
+(``all_errors.pt``).  ``--start_from_stage`` resumes from the saved files.  With ``--visualize``,
+``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
+that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
+they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
+reference, one command uses every visible GPU — it starts one rank per GPU under ``torch.distributed.run`` (``--num_gpus`` to pick
 fewer); launching it under ``torch.distributed.run`` yourself works too (every rank seeded alike:
 ``--seed``).
 """
@@ -94,6 +96,7 @@ def main(argv=None):
                                      return_regressor_human36m, return_regressor_visible)
     from .optimize import optimize_embedding
     from .optimize_token import load_ldm
+    from .visualize import visualize_attn_maps
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -132,6 +135,13 @@ def main(argv=None):
         if rank0:
             torch.save(indices, os.path.join(args.save_folder, "indices.pt"))
             print("indices:", indices.tolist(), flush=True)
+        if args.visualize:   # main.py:271-292
+            visualize_attn_maps(
+                ldm, embedding, indices, noise_level=args.noise_level, num_tokens=args.num_tokens, layers=args.layers,
+                num_points=args.top_k, augmentation_iterations=args.augmentation_iterations,
+                dataset_loc=args.dataset_loc, save_folder=args.save_folder, visualize=args.visualize,
+                device=args.device, dataset_name=args.dataset_name, controllers=controllers, num_gpus=num_gpus,
+                max_loc_strategy=args.max_loc_strategy, validation=args.validation, **aug)
     else:
         indices = _load(args.save_folder, "indices.pt", args.device).detach()
     if stage <= 2:
@@ -163,6 +173,13 @@ def main(argv=None):
     regressor = torch.tensor(regressor).to(torch.float32)
     if rank0:
         torch.save(regressor, os.path.join(args.save_folder, "regressor.pt"))
+    if args.visualize:   # main.py:370-391
+        visualize_attn_maps(
+            ldm, embedding, indices, num_tokens=args.num_tokens, layers=args.layers, noise_level=args.noise_level,
+            num_points=args.top_k, regressor=regressor.to(args.device), dataset_loc=args.dataset_loc,
+            save_folder=args.save_folder, device=args.device, dataset_name=args.dataset_name,
+            controllers=controllers, num_gpus=num_gpus, max_loc_strategy=args.max_loc_strategy,
+            validation=args.validation, augmentation_iterations=args.augmentation_iterations, **aug)
     evaluate(ldm, embedding, indices, regressor.to(args.device), num_tokens=args.num_tokens,
              augmentation_iterations=args.augmentation_iterations, save_folder=args.save_folder,
              evaluation_method=args.evaluation_method, max_loc_strategy=args.max_loc_strategy, **common, **aug)

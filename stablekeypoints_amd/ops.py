@@ -1923,3 +1923,120 @@ def conv3x3(x, weight, bias=None, residual=None):
         y = torch.nn.functional.conv2d(x, weight, bias, 1, 1)
         return y if residual is None else residual + y
     return Conv3x3.apply(x, weight, bias, residual)
+
+
+# --------------------------------------------------------------------------- A17 visualisation sheets
+TAB10 = ((31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75),
+         (227, 119, 194), (127, 127, 127), (188, 189, 34), (23, 190, 207))
+# viridis at 0, 32, …, 224, 255 of 256 (the fallback table joins them linearly)
+_VIRIDIS_ANCHORS = ((0, (0.267004, 0.004874, 0.329415)), (32, (0.278826, 0.175490, 0.483397)),
+                    (64, (0.229739, 0.322361, 0.545706)), (96, (0.172719, 0.448791, 0.557885)),
+                    (128, (0.127568, 0.566949, 0.550556)), (160, (0.157851, 0.683765, 0.501686)),
+                    (192, (0.369214, 0.788888, 0.382914)), (224, (0.678489, 0.863742, 0.189503)),
+                    (255, (0.993248, 0.906157, 0.143936)))
+_LUT_CACHE = {}
+
+
+def default_colors(K):
+    """(K, 3) uint8 marker colours: the ten "tab10" colours for K <= 10, else K evenly spaced hues."""
+    if K <= 10:
+        rows = TAB10[:K]
+    else:
+        import colorsys
+        rows = [tuple(int(round(255 * c)) for c in colorsys.hsv_to_rgb(j / K, 0.9, 1.0)) for j in range(K)]
+    return torch.tensor(rows, dtype=torch.uint8).reshape(K, 3)
+
+
+def fallback_lut():
+    """(256, 3) fp32 in [0, 1]: piecewise-linear through nine viridis anchor colours."""
+    lut = torch.empty(256, 3, dtype=F32)
+    for (i0, c0), (i1, c1) in zip(_VIRIDIS_ANCHORS[:-1], _VIRIDIS_ANCHORS[1:]):
+        t = torch.arange(i0, i1 + 1, dtype=torch.float64).sub(i0).div(i1 - i0)[:, None]
+        lut[i0:i1 + 1] = (torch.tensor(c0, dtype=torch.float64) * (1 - t) + torch.tensor(c1, dtype=torch.float64) * t).float()
+    return lut.clamp_(0.0, 1.0)
+
+
+def default_lut():
+    """matplotlib's viridis sampled at 256 points when matplotlib imports, else ``fallback_lut``."""
+    try:
+        import matplotlib
+        import numpy as np
+        cm = matplotlib.colormaps["viridis"]
+        return torch.tensor(np.asarray(cm(np.linspace(0.0, 1.0, 256)))[:, :3], dtype=F32).contiguous()
+    except ImportError:
+        return fallback_lut()
+
+
+def map_range(maps):
+    """(n, h, w) -> (n, 2) per-map (min, max); (NaN, NaN) = "no overlay" for a map that holds a
+    non-finite value or is constant (skp_map_range)."""
+    _lib.require_device(maps)
+    maps = _c(maps)
+    n, h, w = maps.shape
+    out = torch.empty(n, 2, device=maps.device, dtype=F32)
+    call("skp_map_range", ptr(maps), n, h, w, ptr(out), stream(maps.device))
+    return out
+
+
+def sheet_shape(H, W, rows, cols, downscale=1, pad=2):
+    """(Hs, Ws) of a rows × cols sheet of (H, W) images."""
+    return rows * (H // downscale + pad) + pad, cols * (W // downscale + pad) + pad
+
+
+def render_sheet(images, maps=None, points=None, *, rows, cols, downscale=1, pad=2, alpha=0.7, radius=None,
+                 colors=None, lut=None, overlay=None):
+    """One (Hs, Ws, 3) uint8 sheet of rows × cols tiles (skp_render_sheet; visualize.py:40-73, 105-138).
+
+    ``images`` (n, 3, H, W) in [0, 1]; ``maps`` (n, h, w) heat overlay at ``alpha`` through
+    ``lut`` ((256, 3) in [0, 1], default viridis); ``points`` (n, K, 2) normalised (row, col)
+    markers of ``radius`` output pixels (default max(2, th/32)) in ``colors`` ((K, 3) uint8,
+    default ``default_colors``); ``overlay`` (n,) bool, False = that tile shows the plain image.
+    """
+    _lib.require_device(images, maps, points)
+    images = _c(images)
+    n, C, H, W = images.shape
+    if C != 3:
+        raise ValueError(f"render_sheet: images must be (n, 3, H, W), got {tuple(images.shape)}")
+    dev = images.device
+    f = int(downscale)
+    h = w = 0
+    rng = None
+    if maps is not None:
+        maps = _c(maps)
+        if maps.dim() != 3 or maps.shape[0] != n:
+            raise ValueError(f"render_sheet: maps must be ({n}, h, w), got {tuple(maps.shape)}")
+        h, w = maps.shape[1:]
+        rng = map_range(maps)
+        if overlay is not None:
+            keep = torch.as_tensor(overlay, dtype=torch.bool).to(dev)
+            if keep.shape != (n,):
+                raise ValueError(f"render_sheet: overlay must be ({n},), got {tuple(keep.shape)}")
+            rng[~keep] = float("nan")
+        if lut is None:
+            if dev not in _LUT_CACHE:
+                _LUT_CACHE[dev] = default_lut().to(dev)
+            lut = _LUT_CACHE[dev]
+        lut = _c(lut.to(dev))
+        if tuple(lut.shape) != (256, 3):
+            raise ValueError(f"render_sheet: lut must be (256, 3), got {tuple(lut.shape)}")
+    K = 0
+    if points is not None:
+        points = _c(points)
+        if points.dim() != 3 or points.shape[0] != n or points.shape[2] != 2:
+            raise ValueError(f"render_sheet: points must be ({n}, K, 2), got {tuple(points.shape)}")
+        K = points.shape[1]
+    if K:
+        colors = default_colors(K) if colors is None else torch.as_tensor(colors)
+        if colors.dtype != torch.uint8 or tuple(colors.shape) != (K, 3):
+            raise ValueError(f"render_sheet: colors must be ({K}, 3) uint8")
+        colors = colors.to(dev).contiguous()
+        if radius is None:
+            radius = max(2.0, (H // max(f, 1)) / 32.0)
+    else:
+        points = colors = None
+    Hs, Ws = sheet_shape(H, W, rows, cols, max(f, 1), pad)
+    out = torch.empty(Hs, Ws, 3, device=dev, dtype=torch.uint8)
+    call("skp_render_sheet", ptr(images), n, H, W, ptr(maps), h, w, ptr(rng), ptr(lut) if maps is not None else None,
+         float(alpha), ptr(points), K, float(radius or 0.0), ptr(colors), int(rows), int(cols), f, int(pad), ptr(out),
+         stream(dev))
+    return out
