@@ -425,6 +425,27 @@ int skp_render_sheet(const float* images, int n, int H, int W, const float* maps
                      const unsigned char* colors, int rows, int cols, int f, int pad, unsigned char* out,
                      void* stream);
 
+/* ---------------------------------------------------------------- A18 test-time-augmentation reduce
+ * The tail of eval.run_image_with_context_augmented (eval.py:327-355: sum_samples +=
+ * inverse(maps), num_samples += inverse(ones), sum / num, NaN -> 0) followed by eval.find_max_pixel
+ * (eval.py:39-60), for B images at once without the full-size sums in memory.
+ *   maps (B, C, n, S, S): n token maps of C warped copies of each image; theta_inv (B, C, 2, 3):
+ *   each copy's inverse theta; pos (B, n, 2) = (row + 0.5, col + 0.5); avg (B, n, S, S) or NULL.
+ * For image b, token t and pixel p, with the grid and bilinear sample of skp_affine_warp:
+ *   sum = Σ_c sample(maps[b,c,t], grid(theta_inv[b,c], p)),  num = Σ_c sample(ones, …),
+ *   a = sum / num with NaN -> 0;  pos[b,t] = first-occurrence row-major argmax of a;  avg[b,t,p] = a.
+ * Both sums start from 0.0f and add in copy order c = 0 … C−1, the quotient is IEEE: bit-identical
+ * to skp_affine_warp per copy, `acc = acc + warped`, the division, the NaN fix and skp_argmax2d.
+ * workspace: skp_tta_reduce_workspace(B, n, S) bytes (−1 on a bad shape), 8-B aligned: one
+ * (value, index) partial per image, token and 64 × 4-pixel tile.  Two launches (tiles, then one
+ * merge per image and token; the greater value wins, on equal values the lower index), no atomics:
+ * deterministic.
+ * Rejected before any launch: null pointers (avg excepted), non-positive sizes, S < 2,
+ * B·C·n·S² >= 2^31, B > 65535, a misaligned workspace.                                                       */
+int skp_tta_reduce_workspace(int B, int n, int S);
+int skp_tta_reduce(const float* maps, int B, int C, int n, int S, const float* theta_inv, float* pos, float* avg,
+                   void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

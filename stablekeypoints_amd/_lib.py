@@ -93,6 +93,8 @@ _SIGS = {
     "skp_map_range": [_p, _c_int, _c_int, _c_int, _p, _p],
     "skp_render_sheet": [_p, _c_int, _c_int, _c_int, _p, _c_int, _c_int, _p, _p, _c_float, _p, _c_int, _c_float, _p,
                          _c_int, _c_int, _c_int, _c_int, _p, _p],
+    "skp_tta_reduce_workspace": [_c_int, _c_int, _c_int],
+    "skp_tta_reduce": [_p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p],
     "skp_version": [],
 }
 

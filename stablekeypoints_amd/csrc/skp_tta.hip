@@ -1,0 +1,252 @@
+// A18: the test-time-augmentation reduce — the inverse warps, the two sums over the copies, the
+// ratio, the NaN fix and the argmax of eval.run_image_with_context_augmented in one pass, for gfx950.
+//
+// Reference: eval.py:327-355 (sum_samples += inverse(maps), num_samples += inverse(ones),
+// attention_maps = sum / num, NaN -> 0) and eval.py:39-60 (find_max_pixel: first-occurrence
+// row-major argmax, position = (row + 0.5, col + 0.5)).  The reference holds the full-size average
+// only to read its argmax; here every captured map is read once and the keypoints leave directly
+// (the average is written only on request).
+//
+// Arithmetic is the sequential composition's, bit for bit: grid_point and sample_ones of skp_warp.h,
+// its sample() restated on paired loads (sample_taps: the same products and sums, unfused), both
+// sums from 0.0f in copy order with __fadd_rn, __fdiv_rn, NaN -> 0 before the argmax.
+//
+// Two launches, no atomics: the tile kernel (one workgroup per image and 64 x 4-pixel piece of a
+// four-row band) leaves one (value, linear index) partial per token and tile; the merge kernel
+// reduces each (image, token)'s partials (the greater value wins, on equal values the lower index).
+#include "skp_warp.h"
+
+using namespace skp;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / WAVE;
+// Tokens per pass over a pixel's copies: the pixel's C grid records (theta is wave-uniform, the
+// record depends on pixel and copy only) are formed once per pass and serve all its tokens; the
+// sums stay in registers.  10 = the pipeline's top_k, so its maps take one pass.
+constexpr int kTok = 10;
+static_assert(kTok <= 15, "the rest after the kTok passes is split into passes of 8, 4, 2 and 1");
+constexpr int kNoIndex = 0x7fffffff;
+
+__device__ __forceinline__ bool better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+
+// In-wave argmax of NaN-free values: the maximum through the DPP reduction, then the lowest index
+// among the lanes that hold it.  Every lane ends with the result.
+__device__ __forceinline__ void wave_best(float& v, int& i) {
+  const float m = wave_max(v);
+  int c = v == m ? i : kNoIndex;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c = min(c, __shfl_xor(c, o, 64));
+  v = m;
+  i = c;
+}
+
+// A workgroup takes a tile of kTileW x kTileH pixels, one pixel per thread, each wave a 16 x 4
+// block of it: a rotated copy's taps of a 16 x 4 block fall on about 4-12 source rows, those of 64
+// pixels of one row on up to 32, and every source row a wave instruction touches is a cache line
+// of its own.
+constexpr int kTileW = 64, kTileH = 4;
+__host__ __device__ inline int tiles_x(int S) { return (S + kTileW - 1) / kTileW; }
+__host__ __device__ inline int tiles_y(int S) { return (S + kTileH - 1) / kTileH; }
+
+// A grid record ready for many planes.  The two taps of a row are neighbours in memory, so each
+// row goes as ONE 8-byte load at a column clamped into [0, S − 2] (every load lands inside the
+// plane and needs no branch, so all of a pass's 2·NT loads are in flight together; the tile kernel
+// is bound by the number of gather instructions, not by bytes).  `swap`: the clamp moved the pair
+// by one column (x0 = −1 or S − 1), so the tap that is in range sits in the other half.  S >= 2.
+struct Taps {
+  int off[2];     // north and south row: offset of the pair
+  bool swap;
+  bool ok[4];     // the tap counts (is inside the plane)
+  float w[4];
+};
+struct __attribute__((packed, aligned(4))) Pair {
+  float a, b;
+};
+__device__ __forceinline__ Taps taps_of(const Bilin& b, int S) {
+  Taps t;
+  const int xb = max(min(b.x0, S - 2), 0);
+  t.swap = xb != b.x0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int xx = b.x0 + (k & 1), yy = b.y0 + (k >> 1);
+    t.ok[k] = xx >= 0 && xx < S && yy >= 0 && yy < S;
+    t.w[k] = b.w[k];
+  }
+#pragma unroll
+  for (int r = 0; r < 2; ++r) t.off[r] = min(max(b.y0 + r, 0), S - 1) * S + xb;
+  return t;
+}
+// sample() of skp_warp.h on a Taps record and its two loaded pairs: ((v_nw·nw + v_ne·ne) + v_sw·sw)
+// + v_se·se with every product and sum rounded on its own.  __fmul_rn / __fadd_rn are plain * and +
+// to the compiler, which may contract them (it does not in skp_affine_warp's kernel, and did here),
+// so the products and sums stand under contract(off).
+__device__ __forceinline__ float sample_taps(const Pair (&raw)[2], const Taps& t) {
+#pragma clang fp contract(off)
+  float out = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const Pair& r = raw[k >> 1];
+    const float at = (k & 1) ? (t.swap ? r.a : r.b) : (t.swap ? r.b : r.a);
+    const float v = t.ok[k] ? at : 0.0f;
+    const float prod = v * t.w[k];
+    out = k == 0 ? prod : out + prod;
+  }
+  return out;
+}
+
+struct TileArgs {
+  const float* maps;        // (B, C, n, S, S)
+  const float* theta_inv;   // (B, C, 2, 3)
+  float* avg;               // (B, n, S, S) or null
+  float* part_v;            // (B, n, tiles)
+  int* part_i;
+  int C, n, S;
+};
+
+// Tokens t0 … t0 + NT − 1 of this thread's pixel: one pass over the copies, the sums in registers.
+template <int NT>
+__device__ __forceinline__ void tile_pass(const TileArgs& A, int t0, int b, int x, int y, bool inside, int p,
+                                          float (*s_v)[kWaves], int (*s_i)[kWaves]) {
+  const int S = A.S, SS = S * S;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float bv[NT];
+  int bi[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    bv[j] = -INFINITY;
+    bi[j] = kNoIndex;
+  }
+  if (inside) {
+    const float* th = A.theta_inv + (size_t)b * A.C * 6;
+    float sum[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) sum[j] = 0.0f;
+    float num = 0.0f;
+    for (int c = 0; c < A.C; ++c) {
+      const Bilin g = grid_point(th + 6 * c, y, x, S, S);
+      num = __fadd_rn(num, sample_ones(g, S, S));
+      const Taps t = taps_of(g, S);
+      const float* plane = A.maps + (((size_t)b * A.C + c) * A.n + t0) * SS;
+      Pair raw[NT][2];   // every load of the pass before the first use
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) raw[j][r] = *reinterpret_cast<const Pair*>(plane + (size_t)j * SS + t.off[r]);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) sum[j] = __fadd_rn(sum[j], sample_taps(raw[j], t));
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      float a = __fdiv_rn(sum[j], num);
+      a = a != a ? 0.0f : a;
+      if (A.avg) A.avg[((size_t)b * A.n + t0 + j) * SS + p] = a;
+      bv[j] = a;
+      bi[j] = p;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    wave_best(bv[j], bi[j]);
+    if (lane == 0) {
+      s_v[j][wid] = bv[j];
+      s_i[j][wid] = bi[j];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < NT) {
+    const int j = threadIdx.x;
+    float v = s_v[j][0];
+    int i = s_i[j][0];
+#pragma unroll
+    for (int k = 1; k < kWaves; ++k)
+      if (better(s_v[j][k], s_i[j][k], v, i)) {
+        v = s_v[j][k];
+        i = s_i[j][k];
+      }
+    const size_t o = ((size_t)b * A.n + t0 + j) * gridDim.x + blockIdx.x;
+    A.part_v[o] = v;
+    A.part_i[o] = i;
+  }
+  __syncthreads();
+}
+
+// grid (tiles_x · tiles_y, B).  The tokens go in passes of kTok, the rest in passes of 8, 4, 2, 1
+// (compile-time counts: no branch between a pass's loads).  Four waves per SIMD are asked for, not
+// eight: a pass holds 4·kTok loaded values, and one image of 512² is four waves per SIMD anyway.
+__global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgs A) {
+  __shared__ float s_v[kTok][kWaves];
+  __shared__ int s_i[kTok][kWaves];
+  const int b = blockIdx.y, tile = blockIdx.x, S = A.S;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int x = (tile % tiles_x(S)) * kTileW + wid * 16 + (lane & 15);
+  const int y = (tile / tiles_x(S)) * kTileH + (lane >> 4);
+  const bool inside = x < S && y < S;
+  const int p = inside ? y * S + x : 0;
+  int t0 = 0;
+  for (; t0 + kTok <= A.n; t0 += kTok) tile_pass<kTok>(A, t0, b, x, y, inside, p, s_v, s_i);
+  const int rest = A.n - t0;   // < kTok <= 15
+  if (rest & 8) {
+    tile_pass<8>(A, t0, b, x, y, inside, p, s_v, s_i);
+    t0 += 8;
+  }
+  if (rest & 4) {
+    tile_pass<4>(A, t0, b, x, y, inside, p, s_v, s_i);
+    t0 += 4;
+  }
+  if (rest & 2) {
+    tile_pass<2>(A, t0, b, x, y, inside, p, s_v, s_i);
+    t0 += 2;
+  }
+  if (rest & 1) tile_pass<1>(A, t0, b, x, y, inside, p, s_v, s_i);
+}
+
+// One wave per (image, token): the best of its `parts` partials -> pos (row + 0.5, col + 0.5).
+__global__ __launch_bounds__(WAVE) void tta_merge_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i,
+                                                         int parts, int S, float* __restrict__ pos) {
+  const size_t o = (size_t)blockIdx.x * parts;
+  float v = -INFINITY;
+  int i = kNoIndex;
+  for (int k = threadIdx.x; k < parts; k += WAVE)
+    if (better(part_v[o + k], part_i[o + k], v, i)) {
+      v = part_v[o + k];
+      i = part_i[o + k];
+    }
+  wave_best(v, i);
+  if (threadIdx.x == 0) {
+    pos[2 * (size_t)blockIdx.x] = (float)(i / S) + 0.5f;
+    pos[2 * (size_t)blockIdx.x + 1] = (float)(i % S) + 0.5f;
+  }
+}
+
+}  // namespace
+
+extern "C" int skp_tta_reduce_workspace(int B, int n, int S) {
+  if (B <= 0 || n <= 0 || S < 2) return -1;
+  const long long bytes = (long long)B * n * tiles_x(S) * tiles_y(S) * 8;
+  return bytes < (1ll << 31) ? (int)bytes : -1;
+}
+
+extern "C" int skp_tta_reduce(const float* maps, int B, int C, int n, int S, const float* theta_inv, float* pos,
+                              float* avg, void* workspace, void* stream) {
+  SKP_CHECK_ARG(maps && theta_inv && pos && workspace, "null pointer");
+  SKP_CHECK_ARG(B > 0 && C > 0 && n > 0 && S > 0, "non-positive shape");
+  SKP_CHECK_ARG(S >= 2, "S must be at least 2 (the two taps of a row are loaded as a pair)");
+  SKP_CHECK_ARG(S < 46341 && (long long)B * C * n * S * S < (1ll << 31), "maps of 2^31 elements or more");
+  SKP_CHECK_ARG(B <= 65535, "more than 65535 images");
+  SKP_CHECK_ARG(skp_tta_reduce_workspace(B, n, S) > 0, "workspace of 2^31 bytes or more");
+  SKP_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
+  const int tiles = tiles_x(S) * tiles_y(S);
+  float* part_v = static_cast<float*>(workspace);
+  int* part_i = reinterpret_cast<int*>(part_v + (size_t)B * n * tiles);
+  hipStream_t st = as_stream(stream);
+  TileArgs A;
+  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg, A.part_v = part_v, A.part_i = part_i;
+  A.C = C, A.n = n, A.S = S;
+  hipLaunchKernelGGL(tta_tile_kernel, dim3(tiles, B), dim3(kThreads), 0, st, A);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tta_merge_kernel, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, tiles, S, pos);
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}

@@ -6,6 +6,9 @@ reference's semantics (first-occurrence argmax, NaN is max, in-place mutation in
 ``pixel_from_weighted_avg``).  ``run_image_with_context_augmented`` (``:197-355``) is the
 test-time-augmentation average on the same kernels; ``evaluate`` (``:374-539``) regresses
 keypoints from it and scores them with the reference's five metrics (``keypoint_error``).
+``predict_keypoints`` (extra) returns the keypoints of a batch of unlabelled images: batched
+captures and the whole TTA reduce (inverse warps, sums, ratio, argmax) in one kernel,
+``skp_tta_reduce``.
 """
 import contextlib
 import os
@@ -219,3 +222,79 @@ def evaluate(ldm, context, indices, regressor, device="cuda", from_where=("down_
     mean = float(torch.tensor(values).mean()) if values else float("nan")
     print(f"mean distance: {mean}", flush=True)
     return mean
+
+
+@torch.no_grad()
+def predict_keypoints(ldm, images, context, indices, regressor=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
+                      noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
+                      augmentation_iterations=20, max_loc_strategy="argmax", controllers=None, upscale_size=512,
+                      image_batch=None, return_maps=False):
+    """Keypoints of a batch of unlabelled images (extra: the use the reference's demo ends in,
+    ``visualize_keypoints``: TTA maps → ``find_max_pixel(map) / 512``, which draws the points and
+    does not return them).
+
+    ``images`` is (B, 3, H, W) in [0, 1] (a single (3, H, W) image is B = 1).  For image 0, then
+    image 1, … ``augmentation_iterations`` thetas are drawn with ``draw_theta(1)`` — the order in
+    which successive ``run_image_with_context_augmented`` calls would draw them.  The warped copies
+    are captured per copy (``run_and_find_attn_per_image``), whole images' worth of copies per pass
+    as ``AUG_BATCH_PIXELS`` allows (``image_batch`` overrides the images per pass; an image whose
+    copies exceed the bound gets a pass of its own), and each pass is reduced by ``ops.tta_reduce``:
+    inverse warps, sums in copy order, ratio, NaN → 0 and argmax in one kernel, without the
+    full-size average in memory unless it is asked for.
+
+    Returns the (B, n, 2) keypoints (row, col) = position / ``upscale_size``: the argmax, or with
+    ``max_loc_strategy="weighted_avg"`` ``pixel_from_weighted_avg`` of the averages.  With a
+    ``regressor`` (2n, 2K) also ``((p.reshape(B, -1) − 0.5) @ W + 0.5).reshape(B, -1, 2)``; with
+    ``return_maps`` also the (B, n, S, S) averages.  More than one output comes as a tuple in that
+    order.  Single process only: under a process group of more than one rank it raises.
+    """
+    from .optimize import _world
+    if _world()[0] > 1:
+        raise ValueError("predict_keypoints runs in a single process (world size must be 1)")
+    if max_loc_strategy not in ("argmax", "weighted_avg"):
+        raise ValueError("max_loc_strategy must be 'argmax' or 'weighted_avg'")
+    imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
+    if imgs.dim() == 3:
+        imgs = imgs[None]
+    if imgs.dim() != 4 or imgs.shape[1] != 3:
+        raise ValueError(f"images must be (B, 3, H, W) or (3, H, W), got {tuple(imgs.shape)}")
+    imgs = imgs.to(device, torch.float32)
+    B, C, S = imgs.shape[0], int(augmentation_iterations), int(upscale_size)
+    if C < 1:
+        raise ValueError("augmentation_iterations must be at least 1")
+    n = len(indices)
+    T = RandomAffineWithInverse(degrees=augment_degrees, scale=augment_scale, translate=augment_translate)
+    theta = torch.cat([T.draw_theta(1) for _ in range(B * C)]).reshape(B, C, 2, 3)
+    if image_batch is None:
+        image_batch = AUG_BATCH_PIXELS // (imgs.shape[-1] * imgs.shape[-2] * C)
+    per_pass = max(1, int(image_batch))
+    weighted = max_loc_strategy == "weighted_avg"
+    want_avg = weighted or return_maps
+    pos, avgs = [], []
+    for i0 in range(0, B, per_pass):
+        nb = min(per_pass, B - i0)
+        aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
+        with _reproducible_convolutions():
+            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
+                                                        layers=layers, upsample_res=S, indices=indices,
+                                                        controllers=controllers)
+        maps = torch.stack([per[k][b] for b in range(nb * C) for k in range(len(per))])
+        if tuple(maps.shape) != (nb * C, n, S, S):
+            raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
+        p, avg = ops.tta_reduce(maps.reshape(nb, C, n, S, S), T.theta_inverse().reshape(nb, C, 2, 3).to(device),
+                                return_avg=want_avg)
+        del maps, per
+        if weighted:   # pixel_from_weighted_avg zeroes its input in place: the returned maps stay whole
+            p = pixel_from_weighted_avg(avg.clone().reshape(nb * n, S, S) if return_maps else
+                                        avg.reshape(nb * n, S, S)).reshape(nb, n, 2)
+        pos.append(p)
+        if return_maps:
+            avgs.append(avg)
+    kp = torch.cat(pos) / S
+    out = [kp]
+    if regressor is not None:
+        W = regressor.to(kp.device, torch.float32)
+        out.append(((kp.reshape(B, -1) - 0.5) @ W + 0.5).reshape(B, -1, 2))
+    if return_maps:
+        out.append(torch.cat(avgs))
+    return out[0] if len(out) == 1 else tuple(out)

@@ -3,7 +3,10 @@
 optimize (``optimize_embedding`` → ``embedding.pt``) → find_indices (``find_best_indices`` →
 ``indices.pt``) → precompute (``precompute_all_keypoints`` → ``source_keypoints.pt``,
 ``target_keypoints.pt``, ``visible.pt``) → regressor (``regressor.pt``) → evaluate
-(``all_errors.pt``).  ``--start_from_stage`` resumes from the saved files.  With ``--visualize``,
+(``all_errors.pt``).  ``--start_from_stage`` resumes from the saved files; ``--start_from_stage predict``
+(extra) instead writes the keypoints of the dataset's images — the stage for unlabelled ``custom``
+folders — from ``embedding.pt`` and ``indices.pt`` (``keypoints.pt``, ``keypoints.csv``, and
+``regressed_keypoints.pt`` when ``regressor.pt`` is there) and stops, in one process.  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -18,6 +21,9 @@ import sys
 import torch
 
 
+STAGES = ("optimize", "find_indices", "precompute", "evaluate")
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="optimize a class embedding")
     p.add_argument("--model_type", type=str, default="runwayml/stable-diffusion-v1-5",
@@ -30,8 +36,9 @@ def build_parser():
                    choices=["celeba_aligned", "celeba_wild", "cub_aligned", "cub_001", "cub_002", "cub_003", "cub_all",
                             "deepfashion", "taichi", "human3.6m", "unaligned_human3.6m", "custom", "synthetic"])
     p.add_argument("--max_len", type=int, default=-1)
-    p.add_argument("--start_from_stage", choices=["optimize", "find_indices", "precompute", "evaluate"],
-                   default="optimize")
+    p.add_argument("--start_from_stage", choices=list(STAGES) + ["predict"], default="optimize",
+                   help="resume the pipeline from this stage's saved files; 'predict' only writes the keypoints of "
+                        "the dataset's images (keypoints.pt, keypoints.csv) from embedding.pt and indices.pt")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--wandb", action="store_true")
     p.add_argument("--lr", type=float, default=5e-3)
@@ -69,8 +76,9 @@ def build_parser():
 
 def ranks_to_start(args, visible, env):
     """How many ranks this command starts: 1 when already running as a rank (``env``) or with at
-    most one GPU, else ``--num_gpus`` (every visible GPU by default)."""
-    if env is not None:
+    most one GPU, and for the single-process ``predict`` stage, else ``--num_gpus`` (every visible GPU by
+    default)."""
+    if env is not None or args.start_from_stage == "predict":   # predict runs in this process, on --device
         return 1
     n = visible if args.num_gpus < 0 else args.num_gpus
     if n > max(visible, 1):
@@ -81,6 +89,61 @@ def ranks_to_start(args, visible, env):
 def _load(folder, name, device=None):
     t = torch.load(os.path.join(folder, name), weights_only=True)
     return t.to(device) if (device is not None and t is not None) else t
+
+
+def _image_names(dataset):
+    """File name per dataset index where the reader has ``image_files`` (``custom``), else None."""
+    if isinstance(dataset, torch.utils.data.Subset):
+        names = _image_names(dataset.dataset)
+        return None if names is None else [names[i] for i in dataset.indices]
+    names = getattr(dataset, "image_files", None)
+    return None if names is None else list(names)
+
+
+def predict_stage(args, ldm, controllers, batch=4):
+    """``--start_from_stage predict``: the keypoints of every image of the dataset (built as
+    ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
+    the saved ``embedding.pt`` and ``indices.pt``.  Writes ``keypoints.pt`` (M, n, 2) = (row, col) / 512,
+    ``regressed_keypoints.pt`` when ``regressor.pt`` is there, and ``keypoints.csv`` (one row per image and no
+    header: index, file name where the reader has one, the n (row, col) pairs, then the regressed pairs)."""
+    import csv
+    from .datasets import make_dataset
+    from .eval import predict_keypoints
+    folder = args.save_folder
+    embedding = _load(folder, "embedding.pt", args.device).detach()
+    indices = _load(folder, "indices.pt", args.device).detach()
+    regressor = _load(folder, "regressor.pt", args.device) if os.path.exists(os.path.join(folder, "regressor.pt")) else None
+    dataset = make_dataset(args.dataset_name, args.dataset_loc, max_len=args.max_len, validation=args.validation,
+                           split="test")
+    names = _image_names(dataset)
+    kps, regs = [], []
+    for i0 in range(0, len(dataset), batch):
+        images = torch.stack([dataset[i]["img"] for i in range(i0, min(i0 + batch, len(dataset)))])
+        out = predict_keypoints(ldm, images, embedding, indices.cpu(), regressor=regressor, device=args.device,
+                                layers=args.layers, noise_level=args.noise_level,
+                                augment_degrees=args.augment_degrees, augment_scale=args.augment_scale,
+                                augment_translate=args.augment_translate,
+                                augmentation_iterations=args.augmentation_iterations,
+                                max_loc_strategy=args.max_loc_strategy, controllers=controllers)
+        kp, reg = out if regressor is not None else (out, None)
+        kps.append(kp.cpu())
+        if reg is not None:
+            regs.append(reg.cpu())
+    n = len(indices)
+    kps = torch.cat(kps) if kps else torch.zeros(0, n, 2)
+    torch.save(kps, os.path.join(folder, "keypoints.pt"))
+    if regressor is not None:
+        regs = torch.cat(regs) if regs else torch.zeros(0, regressor.shape[1] // 2, 2)
+        torch.save(regs, os.path.join(folder, "regressed_keypoints.pt"))
+    with open(os.path.join(folder, "keypoints.csv"), "w", newline="") as fh:
+        w = csv.writer(fh)
+        for i in range(kps.shape[0]):
+            row = [i] + ([names[i]] if names is not None else [])
+            row += [repr(float(v)) for v in kps[i].reshape(-1)]
+            if regressor is not None:
+                row += [repr(float(v)) for v in regs[i].reshape(-1)]
+            w.writerow(row)
+    print(f"predict: {kps.shape[0]} images, {n} keypoints each -> {os.path.join(folder, 'keypoints.pt')}", flush=True)
 
 
 def main(argv=None):
@@ -108,7 +171,9 @@ def main(argv=None):
     ldm, controllers, num_gpus = load_ldm(args.device, args.model_type, feature_upsample_res=args.feature_upsample_res)
     os.makedirs(args.save_folder, exist_ok=True)
     rank0 = int(os.environ.get("RANK", "0")) == 0
-    stage = ["optimize", "find_indices", "precompute", "evaluate"].index(args.start_from_stage)
+    if args.start_from_stage == "predict":
+        return predict_stage(args, ldm, controllers)
+    stage = STAGES.index(args.start_from_stage)
     common = dict(noise_level=args.noise_level, device=args.device, layers=args.layers, dataset_loc=args.dataset_loc,
                   dataset_name=args.dataset_name, controllers=controllers, num_gpus=num_gpus,
                   validation=args.validation)

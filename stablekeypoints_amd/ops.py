@@ -2040,3 +2040,44 @@ def render_sheet(images, maps=None, points=None, *, rows, cols, downscale=1, pad
          float(alpha), ptr(points), K, float(radius or 0.0), ptr(colors), int(rows), int(cols), f, int(pad), ptr(out),
          stream(dev))
     return out
+
+
+# --------------------------------------------------------------------------- A18 TTA reduce
+_TTA_WS = {}   # (device, B, n, S) -> workspace of skp_tta_reduce_workspace bytes
+
+
+def tta_reduce_bytes(B, C, n, S, avg=False):
+    """Byte model of skp_tta_reduce: every captured map read once, the average written on request."""
+    return 4 * B * C * n * S * S + (4 * B * n * S * S if avg else 0)
+
+
+def tta_reduce(maps, theta_inv, return_avg=False):
+    """The TTA reduce of B images in one call (skp_tta_reduce; eval.py:327-355 then :39-60).
+
+    ``maps`` (B, C, n, S, S): n token maps of C warped copies per image; ``theta_inv`` (B, C, 2, 3)
+    each copy's inverse theta.  Returns ``(pos, avg)``: ``pos`` (B, n, 2) = (row + 0.5, col + 0.5)
+    of the first-occurrence argmax of Σ_c warp(maps) / Σ_c warp(ones) with NaN → 0, and that
+    average (B, n, S, S) when ``return_avg``, else None.  Bit-identical to ``affine_warp`` per
+    copy, sums in copy order, the division, the NaN fix and ``find_max_pixel``.
+    """
+    _lib.require_device(maps, theta_inv)
+    if maps.dim() != 5 or maps.shape[-1] != maps.shape[-2]:
+        raise ValueError(f"tta_reduce: maps must be (B, C, n, S, S), got {tuple(maps.shape)}")
+    maps = _c(maps)
+    B, C, n, S, _ = maps.shape
+    if tuple(theta_inv.shape) != (B, C, 2, 3):
+        raise ValueError(f"tta_reduce: theta_inv must be ({B}, {C}, 2, 3), got {tuple(theta_inv.shape)}")
+    dev = maps.device
+    th = _c(theta_inv.to(dev))
+    key = (dev, B, n, S)
+    ws = _TTA_WS.get(key)
+    if ws is None:
+        nbytes = _lib.lib().skp_tta_reduce_workspace(B, n, S)
+        if nbytes <= 0:
+            raise ValueError(f"tta_reduce: bad shape B={B}, n={n}, S={S}")
+        ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
+    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
+    with _timed("skp_tta_reduce", tta_reduce_bytes(B, C, n, S, return_avg)):
+        call("skp_tta_reduce", ptr(maps), B, C, n, S, ptr(th), ptr(pos), ptr(avg), ptr(ws), stream(dev))
+    return pos, avg
