@@ -279,6 +279,13 @@ int skp_groupnorm_bwd(const float* x, const float* dy, const float* gamma, const
 int skp_groupnorm_fwd_part(const float* x, const float* gamma, const float* beta, const float* shift, const float* part,
                            int nseg, int B, int C, long long HW, int G, float eps, int act, float* y, float* stats,
                            double* partial, void* stream);
+/* The statistics of skp_groupnorm_fwd / skp_groupnorm_fwd_part without the apply pass: stats
+ * (B*G*2 floats) = the same (mean, rstd), for a consumer that normalises on load
+ * (skp_wino2_vtransform_gn).  partial as above. */
+int skp_groupnorm_stats(const float* x, const float* shift, int B, int C, long long HW, int G, float eps, float* stats,
+                        double* partial, void* stream);
+int skp_groupnorm_stats_part(const float* part, int nseg, const float* shift, int B, int C, long long HW, int G,
+                             float eps, float* stats, double* partial, void* stream);
 /* skp_groupnorm_bwd plus dres (may be null): dx = GroupNorm-backward(dy) + dres, the gradient of x's
  * other consumer (the ResNet block's residual or shortcut, the spatial transformer's residual) added
  * in the same pass instead of by the autograd engine (diffusers resnet.py / attention.py residuals). */
@@ -387,6 +394,26 @@ int skp_conv3x3_wino2(const float* x, const float* U, const float* bias, const f
  * (diffusers resnet.py) then reads its input once instead of twice. */
 int skp_conv3x3_wino2_gn(const float* x, const float* U, const float* bias, const float* residual, float* y, int B,
                          int C, int K, int H, int W, int nsplit, float* ws, float* gn_part, void* stream);
+/* The same convolution with the input transform done once instead of by each of the K/32 channel-block
+ * workgroups: the V-staged pair for the frozen, gradient-free VAE encoder's GroupNorm → SiLU → 3×3
+ * convolution (diffusers ResnetBlock2D inside Encoder, ptp_utils.py:289-304 image2latent).
+ * skp_wino2_vtransform: V = Bᵀ d B of every 4×4 tile of d = x (B, C, H, W), zero padded; H, W
+ *   multiples of 32, C % 4 == 0.  V holds B·C·H·W/16·40 floats: per half-height block (8 × 4 tiles,
+ *   blocks in image, row, column order) and 4-channel stage one 20-KB slab [4 ch][32 tiles][40]
+ *   whose rows are laid out as U's (positions 0..17 at 0..17, 18..35 at 20..37, zero pads).
+ * skp_wino2_vtransform_gn: the same with d = act(GroupNorm(x + shift)) computed on load from
+ *   stats (B·G·2 floats (mean, rstd), from skp_groupnorm_stats / _stats_part or a forward),
+ *   gamma, beta and shift (B·C floats or NULL): bit for bit the values skp_groupnorm_fwd writes,
+ *   never stored; the padding is of d, not of x.  One pass: reads x, writes V (14 B per element).
+ * skp_conv3x3_wino2_v / _v_gn: skp_conv3x3_wino2 / _gn with V in place of x; same U, epilogues,
+ *   nsplit / ws and gn_part, and the same bits as skp_conv3x3_wino2 on d at the same nsplit. */
+int skp_wino2_vtransform(const float* x, float* V, int B, int C, int H, int W, void* stream);
+int skp_wino2_vtransform_gn(const float* x, const float* stats, const float* gamma, const float* beta,
+                            const float* shift, int G, int act, float* V, int B, int C, int H, int W, void* stream);
+int skp_conv3x3_wino2_v(const float* V, const float* U, const float* bias, const float* residual, float* y, int B,
+                        int C, int K, int H, int W, int nsplit, float* ws, void* stream);
+int skp_conv3x3_wino2_v_gn(const float* V, const float* U, const float* bias, const float* residual, float* y, int B,
+                           int C, int K, int H, int W, int nsplit, float* ws, float* gn_part, void* stream);
 /* diffusers' Downsample2D(padding=0) of the VAE encoder (F.pad(x, (0, 1, 0, 1)) then a 3×3 stride-2
  * convolution; the encoder behind ptp_utils.image2latent, reference ptp_utils.py:289-304):
  * y (B, K, H/2, W/2) = the stride-1 pad-1 convolution of x sampled at (2oy + 1, 2ox + 1), + bias,

@@ -37,6 +37,7 @@
 #include <cstdlib>
 
 #include "skp_common.h"
+#include "skp_gn.h"   // gn_coef, gn_elem: the GroupNorm(+SiLU) fused into the transform pass
 
 using namespace skp;
 
@@ -736,7 +737,13 @@ __device__ __forceinline__ void w2_vmcnt(int n) {
 
 // One wave's whole program for transform half HH (rows 3HH..3HH+2); the kernel branches once
 // on the wave's half so the stage loop is straight-line code for each.
-template <int EPI, int HH, int TXB, int NW>
+//
+// VST (the V-staged form, skp_conv3x3_wino2_v): `x` is not the image but its transform V from
+// skp_wino2_vtransform, one 20-KB slab [4 ch][32 tiles][40] per (half-height block, stage) in
+// U's row layout.  The raw ring and the per-lane transform are replaced by a V ring (sm.R0, sm.R1)
+// filled by LDS-DMA like U; the A operand is read from LDS per stage with the B operand's row
+// pattern.  MFMA order, accumulators and the epilogue are the same code.
+template <int EPI, int HH, int TXB, int NW, bool VST = false>
 __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __restrict__ x, const float* __restrict__ U,
                                            const float* __restrict__ bias, const float* __restrict__ res,
                                            float* __restrict__ y, int C, int K, int H, int W, int img, int x0,
@@ -756,7 +763,8 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   using w2::kUP;
   // raw-input ring of RS slots (lead RS − 1 stages: the input streams from HBM), weight ring
   // of 3 (lead 2: the weights are re-read by every tile block and hit L2)
-  constexpr int RS = (TXB == 4 && NW == 4) ? 2 : (TXB == 8 && NW == 8 && SKP_W2_RS4) ? 4 : 3;
+  static_assert(!VST || (TXB == 8 && NW == 4), "V-staged form: half-height blocks of 4 waves");
+  constexpr int RS = (VST || (TXB == 4 && NW == 4)) ? 2 : (TXB == 8 && NW == 8 && SKP_W2_RS4) ? 4 : 3;
   float *R0 = sm.R0, *R1 = sm.R1, *R2 = sm.R2, *U0 = sm.U0, *U1 = sm.U1, *U2 = sm.U2;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wm = wv % (NW / 2);
@@ -855,48 +863,101 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
     }
   };
 
-  // prologue: the DMAs of "steps" −RS..−1 (raw(0..RS−1), U(0), U(1)) in step order; wait for
-  // raw(0) and transform it
-  issue_raw(0, R0);
-  if (RS == 4) issue_raw(1, R1);
-  issue_u(0, U0);
-  if (RS >= 3) issue_raw(RS - 2, RS == 4 ? R2 : R1);
-  if (US == 3 && nst > 1) issue_u(1, U1);
-  issue_raw(RS - 1, RS == 4 ? sm.R3 : RS == 3 ? R2 : R1);
-  w2_vmcnt(nst > 1 ? allow_pro : 0);
-  __syncthreads();
-  w2::W2_TRANSFORM<HH, kRowF>(R0 + roff, a0);
-
-  // stage s: wait for U(s) and raw(s+1); barrier; issue U(s+2) and raw(s+RS) into the slots
-  // freed by stage s-1; transform raw(s+1) (slot (s+1)%RS) and run the MFMAs on U(s) (slot
-  // s%3).  The SIMD partners (waves w, w+4: the two halves) do these in opposite orders.
-  auto step = [&](int s, float* Rn, float* Us, float* Ri, float* Ui, const float (&acur)[18], float (&anext)[18]) {
-    w2_vmcnt(s + 1 < nst ? allow_step : 0);
-    __syncthreads();
-    if (s + US - 1 < nst) issue_u(s + US - 1, Ui);
-    issue_raw(s + RS, Ri);   // past the last stage: empty (zero-length) loads keep the counts
-    const bool tr = s + 1 < nst && !(dbg & 1);
-    if (HH == 0) {
-      if (tr) w2::W2_TRANSFORM<HH, kRowF>(Rn + roff, anext);
-      if (!(dbg & 2)) mfmas(Us, acur);
-    } else {
-      if (!(dbg & 2)) mfmas(Us, acur);
-      if (tr) w2::W2_TRANSFORM<HH, kRowF>(Rn + roff, anext);
-    }
-  };
-  // unrolled by lcm(RS, 3, 2): raw slot s%RS, U slot s%3, A-operand buffer s%2
-  constexpr int PER = RS == 4 ? 12 : RS == 2 ? 2 : 6;
-  float* const Rsl[4] = {R0, R1, R2, sm.R3};
-  float* const Usl[3] = {U0, U1, U2};
-  for (int s0 = 0; s0 < ((dbg & 16) ? 0 : nst); s0 += PER) {
-    step(s0, Rsl[1 % RS], Usl[0], Rsl[0], Usl[US - 1], a0, a1);
+  if constexpr (VST) {
+    // slab of (tile block, stage t): V + ((tb · C/4) + c0/4 + t) · kUF; 20 chunks of 1 KB, 5 per wave
+    const int bw = W >> 5;
+    const size_t tb = (size_t)img * ((H >> 4) * bw) + (size_t)(y0 >> 4) * bw + (x0 >> 5);
+    const float* Vb = x + (tb * (size_t)(C / w2::kCK) + (size_t)(c0 / w2::kCK)) * kUF;
+    auto issue_vu = [&](int t, float* vs_lds, float* us_lds) {
+      const __amdgpu_buffer_rsrc_t rv =
+          __builtin_amdgcn_make_buffer_rsrc((void*)(Vb + (size_t)t * kUF), (short)0, kUF * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t ru =
+          __builtin_amdgcn_make_buffer_rsrc((void*)(Ub + (size_t)t * kUF), (short)0, kUF * 4, 0x00020000);
 #pragma unroll
-    for (int j = 1; j < PER; ++j) {
-      if (s0 + j < nst) {
-        if ((j & 1) == 0) step(s0 + j, Rsl[(j + 1) % RS], Usl[j % US], Rsl[j % RS], Usl[(j + US - 1) % US], a0, a1);
-        else step(s0 + j, Rsl[(j + 1) % RS], Usl[j % US], Rsl[j % RS], Usl[(j + US - 1) % US], a1, a0);
+      for (int m = 0; m < w2::kUInstr / NW; ++m) {
+        const int q = wv + NW * m;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(vs_lds + 256 * q), 16, lane * 16, q * 1024, 0, 0);
+      }
+#pragma unroll
+      for (int m = 0; m < w2::kUInstr / NW; ++m) {
+        const int q = wv + NW * m;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ru, (lds_ptr_t)(us_lds + 256 * q), 16, lane * 16, q * 1024, 0, 0);
+      }
+    };
+    static_assert(w2::kUInstr % NW == 0, "whole chunks per wave");
+    // A operand: V[kc][16 wm + (lane & 15)][18 HH + q], the row pattern of the B operand
+    const int aoff = (kc * 32 + 16 * wm + (lane & 15)) * kUP + 20 * HH;
+    // stage s: wait for V(s), U(s); barrier (everyone is past stage s−1, whose slots are free);
+    // issue V(s+1), U(s+1) into them; read the A operand and run the MFMAs on slot s % 2
+    auto vstep = [&](int s, const float* Vs, const float* Us, float* Vi, float* Ui) {
+      W2_VMCNT(0);
+      __syncthreads();
+      if (s + 1 < nst) issue_vu(s + 1, Vi, Ui);
+      float a[18];
+      const float* vb = Vs + aoff;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float4 v = *reinterpret_cast<const float4*>(vb + 4 * j);
+        a[4 * j] = v.x;
+        a[4 * j + 1] = v.y;
+        a[4 * j + 2] = v.z;
+        a[4 * j + 3] = v.w;
+      }
+      const float2 v2 = *reinterpret_cast<const float2*>(vb + 16);
+      a[16] = v2.x;
+      a[17] = v2.y;
+      mfmas(Us, a);
+    };
+    issue_vu(0, R0, U0);
+    for (int s0 = 0; s0 < nst; s0 += 2) {
+      vstep(s0, R0, U0, R1, U1);
+      if (s0 + 1 < nst) vstep(s0 + 1, R1, U1, R0, U0);
+    }
+  } else {
+    // prologue: the DMAs of "steps" −RS..−1 (raw(0..RS−1), U(0), U(1)) in step order; wait for
+    // raw(0) and transform it
+    issue_raw(0, R0);
+    if (RS == 4) issue_raw(1, R1);
+    issue_u(0, U0);
+    if (RS >= 3) issue_raw(RS - 2, RS == 4 ? R2 : R1);
+    if (US == 3 && nst > 1) issue_u(1, U1);
+    issue_raw(RS - 1, RS == 4 ? sm.R3 : RS == 3 ? R2 : R1);
+    w2_vmcnt(nst > 1 ? allow_pro : 0);
+    __syncthreads();
+    w2::W2_TRANSFORM<HH, kRowF>(R0 + roff, a0);
+
+    // stage s: wait for U(s) and raw(s+1); barrier; issue U(s+2) and raw(s+RS) into the slots
+    // freed by stage s-1; transform raw(s+1) (slot (s+1)%RS) and run the MFMAs on U(s) (slot
+    // s%3).  The SIMD partners (waves w, w+4: the two halves) do these in opposite orders.
+    auto step = [&](int s, float* Rn, float* Us, float* Ri, float* Ui, const float (&acur)[18], float (&anext)[18]) {
+      w2_vmcnt(s + 1 < nst ? allow_step : 0);
+      __syncthreads();
+      if (s + US - 1 < nst) issue_u(s + US - 1, Ui);
+      issue_raw(s + RS, Ri);   // past the last stage: empty (zero-length) loads keep the counts
+      const bool tr = s + 1 < nst && !(dbg & 1);
+      if (HH == 0) {
+        if (tr) w2::W2_TRANSFORM<HH, kRowF>(Rn + roff, anext);
+        if (!(dbg & 2)) mfmas(Us, acur);
+      } else {
+        if (!(dbg & 2)) mfmas(Us, acur);
+        if (tr) w2::W2_TRANSFORM<HH, kRowF>(Rn + roff, anext);
+      }
+    };
+    // unrolled by lcm(RS, 3, 2): raw slot s%RS, U slot s%3, A-operand buffer s%2
+    constexpr int PER = RS == 4 ? 12 : RS == 2 ? 2 : 6;
+    float* const Rsl[4] = {R0, R1, R2, sm.R3};
+    float* const Usl[3] = {U0, U1, U2};
+    for (int s0 = 0; s0 < ((dbg & 16) ? 0 : nst); s0 += PER) {
+      step(s0, Rsl[1 % RS], Usl[0], Rsl[0], Usl[US - 1], a0, a1);
+  #pragma unroll
+      for (int j = 1; j < PER; ++j) {
+        if (s0 + j < nst) {
+          if ((j & 1) == 0) step(s0 + j, Rsl[(j + 1) % RS], Usl[j % US], Rsl[j % RS], Usl[(j + US - 1) % US], a0, a1);
+          else step(s0 + j, Rsl[(j + 1) % RS], Usl[j % US], Rsl[j % RS], Usl[(j + US - 1) % US], a1, a0);
+        }
       }
     }
+
   }
 
   // epilogue: lane holds tiles 4(lane>>4)+r of the wave's 16 (ty = 2wm + (lane>>5),
@@ -1139,6 +1200,104 @@ __global__ void wino2_weights_kernel(const float* __restrict__ w, int K, int C, 
     }
 }
 
+// The V-staged form of wino2_kernel<EPI, 8, 4>: half-height blocks, 4 waves, a two-slot V ring and a
+// two-slot U ring of 20 KB each (80 KB: two workgroups per CU); grid order as wino2_kernel.
+template <int EPI>
+__global__ __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino2v_kernel(
+    const float* __restrict__ V, const float* __restrict__ U, const float* __restrict__ bias,
+    const float* __restrict__ res, float* __restrict__ y, int nimg, int C, int K, int H, int W, int bw, int bpi,
+    int nblk, int nkb, int kb_major, int csplit, int dbg, float2* __restrict__ gnp) {
+  __shared__ __attribute__((aligned(16))) float V0[w2::kUF], V1[w2::kUF], U0[w2::kUF], U1[w2::kUF];
+  static_assert(4 * w2::kUF * 4 <= 80 * 1024, "two workgroups per CU");
+  const int G = gridDim.x;
+  const int g = blockIdx.x;
+  const int Lg = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
+  const int sp = Lg / (nblk * nkb);
+  const int L = Lg - sp * (nblk * nkb);
+  y += (size_t)sp * nimg * K * H * W;
+  int tb, kb;
+  if (kb_major) {
+    kb = L / nblk;
+    tb = L - kb * nblk;
+  } else {
+    tb = L / nkb;
+    kb = L - tb * nkb;
+  }
+  const int img = tb / bpi;
+  const int br = tb - img * bpi;
+  const int by = br / bw;
+  const int x0 = 32 * (br - by * bw), y0 = 16 * by;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const W2Smem sm{V0, V1, nullptr, nullptr, U0, U1, nullptr};
+  const int c0 = sp * csplit;
+  if (wv < 2)
+    wino2_body<EPI, 0, 8, 4, true>(sm, V, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
+  else wino2_body<EPI, 1, 8, 4, true>(sm, V, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
+}
+
+// V = Bᵀ d B of every (image, channel, 4×4 tile) once, d = x or act(GroupNorm(x + shift)) with the
+// zero padding applied to d.  One workgroup per (half-height block of 8 × 4 tiles, 4-channel
+// stage): the 18 × 40-float region rows of the 4 channels go through LDS in wino2_kernel's raw-slot
+// layout (so the patch reads and the transform are that kernel's, bit for bit), each wave
+// transforms one half (rows 3HH..3HH+2) of 16 tiles × 4 channels, and the 20-KB slab
+// [4 ch][32 tiles][40] leaves through LDS as 1-KB wave stores.
+// GN: 0 plain, 1 GroupNorm, 2 GroupNorm + SiLU.
+template <int GN>
+__global__ __launch_bounds__(4 * WAVE) void wino2_vtransform_kernel(
+    const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ shift, int G, float* __restrict__ V, int C, int H, int W,
+    int bw, int bpi) {
+  using Geo = w2::GeoT<8, 4>;
+  constexpr int RR = Geo::RR, RC = Geo::RC, kChF = Geo::CHF, kRowF = Geo::RF;
+  __shared__ __attribute__((aligned(16))) float R[Geo::RAWF];
+  __shared__ __attribute__((aligned(16))) float O[w2::kUF];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int nst = C / w2::kCK;
+  const int tb = blockIdx.x / nst, st = blockIdx.x - tb * nst;
+  const int img = tb / bpi;
+  const int br = tb - img * bpi;
+  const int by = br / bw;
+  const int x0 = 32 * (br - by * bw), y0 = 16 * by;
+  const int cpg = C / (G > 0 ? G : 1);
+  for (int f = tid; f < w2::kCK * RR * RC; f += 4 * WAVE) {
+    const int ch = f / (RR * RC), e = f - ch * (RR * RC);
+    const int row = e / RC, c4 = e - row * RC;
+    const int yy = y0 - 1 + row, xx = x0 - 4 + 4 * c4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+      const int c = w2::kCK * st + ch;
+      v = *reinterpret_cast<const float4*>(x + (((size_t)img * C + c) * H + yy) * W + xx);
+      if (GN) {
+        const int grp = img * G + c / cpg;
+        const GNCoef k = gn_coef(gamma[c], beta[c], stats[2 * grp], stats[2 * grp + 1]);
+        const float t = shift ? shift[(size_t)img * C + c] : 0.0f;
+        v.x = gn_elem<GN == 2>(v.x, t, k); v.y = gn_elem<GN == 2>(v.y, t, k);
+        v.z = gn_elem<GN == 2>(v.z, t, k); v.w = gn_elem<GN == 2>(v.w, t, k);
+      }
+    }
+    *reinterpret_cast<float4*>(R + ch * kChF + row * kRowF + 4 * c4) = v;
+  }
+  __syncthreads();
+  // wino2_body's lane → (stage channel, tile) map: wave (half HH, wm) has tile rows 2wm, 2wm + 1
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int HH = wv >> 1, wm = wv & 1;
+  const int kc = lane >> 4, tx = lane & 7, ty = 2 * wm + ((lane >> 3) & 1);
+  const int roff = kc * kChF + 4 * ty * kRowF + 4 * tx;
+  float a[20];
+  if (HH == 0) w2::W2_TRANSFORM<0, kRowF>(R + roff, a);
+  else w2::W2_TRANSFORM<1, kRowF>(R + roff, a);
+  a[18] = a[19] = 0.0f;   // the row's pads, as in U
+  float* o = O + (kc * 32 + 16 * wm + (lane & 15)) * w2::kUP + 20 * HH;
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    *reinterpret_cast<float4*>(o + 4 * j) = make_float4(a[4 * j], a[4 * j + 1], a[4 * j + 2], a[4 * j + 3]);
+  __syncthreads();
+  float4* out = reinterpret_cast<float4*>(V + (size_t)blockIdx.x * w2::kUF);
+#pragma unroll
+  for (int i = 0; i < w2::kUF / 4 / (4 * WAVE); ++i)
+    out[i * 4 * WAVE + tid] = reinterpret_cast<const float4*>(O)[i * 4 * WAVE + tid];
+}
+
 }  // namespace
 
 extern "C" int skp_wino2_weights(const float* w, int K, int C, int flip, float* U, void* stream) {
@@ -1256,4 +1415,100 @@ extern "C" int skp_conv3x3_wino2_gn(const float* x, const float* U, const float*
 extern "C" int skp_conv3x3_wino2(const float* x, const float* U, const float* bias, const float* residual, float* y,
                                  int B, int C, int K, int H, int W, int nsplit, float* ws, void* stream) {
   return skp_conv3x3_wino2_gn(x, U, bias, residual, y, B, C, K, H, W, nsplit, ws, nullptr, stream);
+}
+
+// ---------------------------------------------------------------- V-staged form (transform once)
+// skp_wino2_vtransform(_gn) writes V = Bᵀ d B of every input tile once; skp_conv3x3_wino2_v(_gn)
+// is skp_conv3x3_wino2(_gn) reading V instead of x.  Bytes model of the transform pass at
+// (B, C, H, W): reads x once from HBM (4 B per element; the halo rows / columns of a block, 1.4×
+// the block in all, come from L2) and writes 40 floats per 4×4 tile (10 B per element): 14 B per
+// element against the 8 B of the gn_apply pass it replaces; the convolution then fetches 10 B per
+// element once from HBM (its other K/32 − 1 reads hit L2) instead of 4.
+namespace {
+int vtransform_launch(const float* x, const float* stats, const float* gamma, const float* beta, const float* shift,
+                      int G, int act, float* V, int B, int C, int H, int W, void* stream) {
+  const int bw = W / 32, bpi = (H / 16) * bw;
+  const long long nwg = (long long)B * bpi * (C / w2::kCK);
+  if (nwg > 0x7fffffffLL) return -2;
+  const dim3 grid((unsigned)nwg), block(4 * WAVE);
+  hipStream_t st = as_stream(stream);
+  if (!stats) hipLaunchKernelGGL(wino2_vtransform_kernel<0>, grid, block, 0, st, x, stats, gamma, beta, shift, G, V, C, H, W, bw, bpi);
+  else if (!act) hipLaunchKernelGGL(wino2_vtransform_kernel<1>, grid, block, 0, st, x, stats, gamma, beta, shift, G, V, C, H, W, bw, bpi);
+  else hipLaunchKernelGGL(wino2_vtransform_kernel<2>, grid, block, 0, st, x, stats, gamma, beta, shift, G, V, C, H, W, bw, bpi);
+  return 0;
+}
+}  // namespace
+
+extern "C" int skp_wino2_vtransform(const float* x, float* V, int B, int C, int H, int W, void* stream) {
+  SKP_CHECK_ARG(x && V, "null pointer");
+  SKP_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "non-positive shape");
+  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
+  SKP_CHECK_ARG(H % 32 == 0 && W % 32 == 0, "H and W must be multiples of 32");
+  SKP_CHECK_ARG(aligned16(x) && aligned16(V), "tensors must be 16-byte aligned");
+  SKP_CHECK_ARG(vtransform_launch(x, nullptr, nullptr, nullptr, nullptr, 0, 0, V, B, C, H, W, stream) == 0,
+                "grid too large");
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
+extern "C" int skp_wino2_vtransform_gn(const float* x, const float* stats, const float* gamma, const float* beta,
+                                       const float* shift, int G, int act, float* V, int B, int C, int H, int W,
+                                       void* stream) {
+  SKP_CHECK_ARG(x && V && stats && gamma && beta, "null pointer");
+  SKP_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "non-positive shape");
+  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
+  SKP_CHECK_ARG(G > 0 && C % G == 0, "C must be divisible by G");
+  SKP_CHECK_ARG(H % 32 == 0 && W % 32 == 0, "H and W must be multiples of 32");
+  SKP_CHECK_ARG(aligned16(x) && aligned16(V), "tensors must be 16-byte aligned");
+  SKP_CHECK_ARG(vtransform_launch(x, stats, gamma, beta, shift, G, act, V, B, C, H, W, stream) == 0, "grid too large");
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
+extern "C" int skp_conv3x3_wino2_v_gn(const float* V, const float* U, const float* bias, const float* residual,
+                                      float* y, int B, int C, int K, int H, int W, int nsplit, float* ws,
+                                      float* gn_part, void* stream) {
+  SKP_CHECK_ARG(V && U && y, "null pointer");
+  SKP_CHECK_ARG(!gn_part || (nsplit == 1 && (reinterpret_cast<uintptr_t>(gn_part) & 7) == 0),
+                "gn_part: one split, 8-byte aligned");
+  SKP_CHECK_ARG(B > 0 && C > 0 && K > 0 && H > 0 && W > 0, "non-positive shape");
+  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
+  SKP_CHECK_ARG(K % w2::kNC == 0, "output channels must be a multiple of 32");
+  SKP_CHECK_ARG(H % 32 == 0 && W % 32 == 0, "H and W must be multiples of 32");
+  SKP_CHECK_ARG(nsplit >= 1 && C % (w2::kCK * nsplit) == 0, "nsplit must divide C into multiples of 4");
+  SKP_CHECK_ARG(nsplit == 1 || ws, "split-K needs a workspace of nsplit·B·K·H·W floats");
+  SKP_CHECK_ARG(aligned16(V) && aligned16(U) && aligned16(y) && (!residual || aligned16(residual)) &&
+                    (!ws || aligned16(ws)),
+                "tensors must be 16-byte aligned");
+  const int bw = W / 32, bpi = (H / 16) * bw;
+  const long long nblk = (long long)B * bpi;
+  const int nkb = K / w2::kNC;
+  SKP_CHECK_ARG(nblk * nkb * nsplit <= 0x7fffffffLL, "grid too large");
+  // tile-major: the K/32 channel blocks of one tile block are consecutive logical workgroups of
+  // one XCD, so a V slab is fetched from HBM once and its other K/32 − 1 reads hit that XCD's L2
+  const int kb_major = 0;
+  const int epi = nsplit > 1 ? 0 : (bias ? 1 : 0) | (residual ? 2 : 0);
+  float* out = nsplit > 1 ? ws : y;
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((unsigned)(nblk * nkb * nsplit));
+  const int fl = SKP_WINO2_DEBUG | wino_nt_flag((long long)B * K * H * W * 4, nsplit);
+  float2* gnp = reinterpret_cast<float2*>(gn_part);
+#define SKP_WV(E)                                                                                                  \
+  hipLaunchKernelGGL((wino2v_kernel<E>), grid, dim3(4 * WAVE), 0, st, V, U, bias, residual, out, B, C, K, H, W, bw, \
+                     bpi, (int)nblk, nkb, kb_major, C / nsplit, fl, gnp)
+  switch (epi) {
+    case 0: SKP_WV(0); break;
+    case 1: SKP_WV(1); break;
+    case 2: SKP_WV(2); break;
+    default: SKP_WV(3); break;
+  }
+#undef SKP_WV
+  SKP_LAUNCH_CHECK();
+  if (nsplit > 1) return splitk_reduce(ws, nsplit, B, K, H * W, bias, residual, y, st);
+  return SKP_OK;
+}
+
+extern "C" int skp_conv3x3_wino2_v(const float* V, const float* U, const float* bias, const float* residual, float* y,
+                                   int B, int C, int K, int H, int W, int nsplit, float* ws, void* stream) {
+  return skp_conv3x3_wino2_v_gn(V, U, bias, residual, y, B, C, K, H, W, nsplit, ws, nullptr, stream);
 }

@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "skp_common.h"
+#include "skp_gn.h"   // sigmoid_of, silu, gn_coef, gn_elem (SKP_GN_FAST)
 
 using namespace skp;
 
@@ -24,26 +25,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kChunk = 16384;   // floats per block (64 KiB)
 
-#ifndef SKP_GN_FAST
-// 1: σ(z) through v_rcp_f32 (1 ulp) instead of the IEEE division sequence, and the channel of a
-// group offset by a 32-bit division (the 64-bit one is a ≈40-instruction sequence per float4);
-// 0: the r04 forms (A/B build)
-#define SKP_GN_FAST 1
-#endif
-__device__ __forceinline__ float sigmoid_of(float z) {
-#if SKP_GN_FAST
-  return __builtin_amdgcn_rcpf(1.0f + __expf(-z));
-#else
-  return 1.0f / (1.0f + __expf(-z));
-#endif
-}
-__device__ __forceinline__ float silu(float z) {
-#if SKP_GN_FAST
-  return z * sigmoid_of(z);
-#else
-  return z / (1.0f + __expf(-z));
-#endif
-}
 __device__ __forceinline__ float silu_grad(float z) {
   const float s = sigmoid_of(z);
   return s * (1.0f + z * (1.0f - s));
@@ -228,11 +209,10 @@ __global__ __launch_bounds__(kThreads) void gn_apply_kernel(const float* __restr
     for_f4(lo, hi, [&](long long e) { return *reinterpret_cast<const float4*>(base + e); },
            [&](long long e, float4 v) {
              const int c = g * sh.cpg + chan_of(e, sh);
-             const float ga = gamma[c] * rstd, be = beta[c] - mean * gamma[c] * rstd;
+             const GNCoef k = gn_coef(gamma[c], beta[c], mean, rstd);
              const float t = shift_of(shift, sh, grp, c);
-             v.x += t; v.y += t; v.z += t; v.w += t;
-             v.x = v.x * ga + be; v.y = v.y * ga + be; v.z = v.z * ga + be; v.w = v.w * ga + be;
-             if (ACT) { v.x = silu(v.x); v.y = silu(v.y); v.z = silu(v.z); v.w = silu(v.w); }
+             v.x = gn_elem<ACT>(v.x, t, k); v.y = gn_elem<ACT>(v.y, t, k);
+             v.z = gn_elem<ACT>(v.z, t, k); v.w = gn_elem<ACT>(v.w, t, k);
              *reinterpret_cast<float4*>(out + e) = v;
            });
   } else {
@@ -442,6 +422,53 @@ extern "C" int skp_groupnorm_fwd_part(const float* x, const float* gamma, const 
   if (vec) { if (act) SKP_GN_APPLY(true, true); else SKP_GN_APPLY(true, false); }
   else { if (act) SKP_GN_APPLY(false, true); else SKP_GN_APPLY(false, false); }
 #undef SKP_GN_APPLY
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
+namespace {
+// (mean, rstd) of every group from its partials, as gn_apply_kernel's first thread computes them
+__global__ __launch_bounds__(kThreads) void gn_moments_kernel(const double* __restrict__ partial, GNShape sh, float eps,
+                                                              float* __restrict__ stats) {
+  const int grp = blockIdx.x * kThreads + threadIdx.x;
+  if (grp >= sh.B * sh.G) return;
+  float mean, rstd;
+  group_moments(partial, grp, sh, eps, mean, rstd);
+  stats[2 * grp] = mean;
+  stats[2 * grp + 1] = rstd;
+}
+}  // namespace
+
+extern "C" int skp_groupnorm_stats(const float* x, const float* shift, int B, int C, long long HW, int G, float eps,
+                                   float* stats, double* partial, void* stream) {
+  SKP_CHECK_ARG(x && stats && partial, "null pointer");
+  GNShape sh;
+  SKP_CHECK_ARG(make_shape(B, C, HW, G, sh), "bad shape (C must be divisible by G)");
+  const bool vec = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  hipStream_t st = as_stream(stream);
+  const dim3 grid(B * G * sh.nsplit);
+  if (vec) hipLaunchKernelGGL(gn_stats_kernel<true>, grid, dim3(kThreads), 0, st, x, shift, sh, partial);
+  else hipLaunchKernelGGL(gn_stats_kernel<false>, grid, dim3(kThreads), 0, st, x, shift, sh, partial);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_moments_kernel, dim3((B * G + kThreads - 1) / kThreads), dim3(kThreads), 0, st, partial, sh, eps,
+                     stats);
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
+extern "C" int skp_groupnorm_stats_part(const float* part, int nseg, const float* shift, int B, int C, long long HW,
+                                        int G, float eps, float* stats, double* partial, void* stream) {
+  SKP_CHECK_ARG(part && stats && partial, "null pointer");
+  SKP_CHECK_ARG(nseg > 0 && HW % nseg == 0, "nseg must divide H·W");
+  GNShape sh;
+  SKP_CHECK_ARG(make_shape(B, C, HW, G, sh), "bad shape (C must be divisible by G)");
+  SKP_CHECK_ARG((reinterpret_cast<uintptr_t>(part) & 7) == 0, "part must be 8-byte aligned");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(gn_part_combine_kernel, dim3(B * G), dim3(kThreads), 0, st, reinterpret_cast<const float2*>(part),
+                     nseg, shift, sh, partial);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_moments_kernel, dim3((B * G + kThreads - 1) / kThreads), dim3(kThreads), 0, st, partial, sh, eps,
+                     stats);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }

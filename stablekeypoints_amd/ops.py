@@ -1925,6 +1925,83 @@ def conv3x3(x, weight, bias=None, residual=None):
     return Conv3x3.apply(x, weight, bias, residual)
 
 
+# --------------------------------------------------------------------------- GroupNorm → 3×3 conv, V-staged
+# The gradient-free GroupNorm(+SiLU) → 3×3 convolution pairs of the frozen VAE encoder as
+# skp_groupnorm_stats → skp_wino2_vtransform_gn → skp_conv3x3_wino2_v: the normalised activation is
+# never stored and every input tile is transformed once instead of K/32 times.  Per-shape choice,
+# measured (tools/wino_time.py --pair, batch 8, each side in a process of its own): a
+# (C, K, H, W) is listed only where the new pair beat gn_apply + wino2 by more than the spread
+# of its own repeats.  Tests add entries to force the path.
+#   (C, K, H, W)          old pair µs  new pair µs   (profiles/r07a_vst_pair_ab.txt, medians of 3)
+#   512→512 @ 64²            606.4        547.1   +9.8%
+#   256→512 @ 128²          1223.9       1101.2  +10.0%
+#   512→512 @ 128²          2205.6       1903.5  +13.7%
+#   128→256 @ 256²          1381.3       1338.6   +3.1%
+#   256→256 @ 256²          2355.3       2241.6   +4.8%
+#   128→128 @ 512²          2698.2       2915.0   −8.0%   stays on wino2: V's extra HBM traffic outweighs it
+WINO_V_SHAPES = {(512, 512, 64, 64), (256, 512, 128, 128), (512, 512, 128, 128), (128, 256, 256, 256),
+                 (256, 256, 256, 256)}
+WINO_V_MIN_BATCH = 4   # the table was measured at batch 8: grids of at least half that size
+
+
+def gn_conv3x3_wins(B, C, K, H, W):
+    """Whether the planner routes act(GroupNorm(x)) → conv3x3 of this shape to the V-staged pair."""
+    return ((C, K, H, W) in WINO_V_SHAPES and B >= WINO_V_MIN_BATCH and C % 4 == 0 and K % 32 == 0
+            and H % 32 == 0 and W % 32 == 0 and WINO_KERNEL == "auto" and not _wino_gemm_ok(B, C, K, H, W))
+
+
+def gn_conv3x3(x, gamma, beta, groups, eps, act, shift, weight, bias=None, residual=None):
+    """conv3x3(act(GroupNorm(x + shift)), weight, bias, residual) without gradient, through the
+    V-staged Winograd pair.  Shapes the kernels do not take are an error (the caller asks
+    gn_conv3x3_wins first); the output carries its GroupNorm statistics partials like conv3x3's."""
+    _lib.require_device(x)
+    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+        raise ValueError("gn_conv3x3: forward only (no gradient reaches the normalised activation)")
+    if weight.requires_grad or gamma.requires_grad or beta.requires_grad:
+        raise ValueError("gn_conv3x3: the parameters must be frozen")
+    pre = _gn_parts_of(x) if GN_EPI else None   # the producing convolution's partials ride on x itself
+    x = _c16(x.detach())
+    B, C, H, W = x.shape
+    K = weight.shape[0]
+    if tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError(f"gn_conv3x3: weight {tuple(weight.shape)} does not fit input {tuple(x.shape)}")
+    if residual is not None:
+        if tuple(residual.shape) != (B, K, H, W):
+            raise ValueError(f"gn_conv3x3: residual {tuple(residual.shape)} is not ({B}, {K}, {H}, {W})")
+        residual = _c16(residual.detach())
+    if shift is not None:
+        shift = _c(shift.detach().reshape(-1, C).to(x.device, F32).expand(B, C))
+    dev = x.device
+    nws = _lib.lib().skp_groupnorm_workspace(B, C, H * W, int(groups))
+    if nws < 0:
+        raise ValueError(f"gn_conv3x3: bad shape {tuple(x.shape)} groups={groups}")
+    part = torch.empty(nws, device=dev, dtype=torch.float64)
+    stats = torch.empty(B * groups * 2, device=dev, dtype=F32)
+    g, b = _c(gamma.detach()), _c(beta.detach())
+    if pre is not None:
+        call("skp_groupnorm_stats_part", ptr(pre[0]), pre[1], ptr(shift), B, C, H * W, int(groups), float(eps),
+             ptr(stats), ptr(part), stream(dev))
+    else:
+        call("skp_groupnorm_stats", ptr(x), ptr(shift), B, C, H * W, int(groups), float(eps), ptr(stats), ptr(part),
+             stream(dev))
+    V = torch.empty(B * C * (H // 4) * (W // 4) * 40, device=dev, dtype=F32)
+    with _timed("skp_wino2_vtransform_gn", 0):
+        call("skp_wino2_vtransform_gn", ptr(x), ptr(stats), ptr(g), ptr(b), ptr(shift), int(groups), int(bool(act)),
+             ptr(V), B, C, H, W, stream(dev))
+    _, nsplit, _ = _wino_plan(B, C, K, H, W)
+    U = _wino_u(weight, False, True)
+    y = torch.empty(B, K, H, W, device=dev, dtype=F32)
+    ws = torch.empty(nsplit, B, K, H, W, device=dev, dtype=F32) if nsplit > 1 else None
+    gnp = torch.empty(B, K, (H // 16) * (W // 32), 2, device=dev, dtype=F32) if GN_EPI and nsplit == 1 else None
+    bias = None if bias is None else _c(bias.detach())
+    with _timed("skp_conv3x3_wino2_v", 0):
+        call("skp_conv3x3_wino2_v_gn", ptr(V), ptr(U), ptr(bias), ptr(residual), ptr(y), B, C, K, H, W, nsplit,
+             ptr(ws), ptr(gnp), stream(dev))
+    if gnp is not None:
+        y._skp_gn = (y._version, gnp, gnp.shape[2])
+    return y
+
+
 # --------------------------------------------------------------------------- A17 visualisation sheets
 TAB10 = ((31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75),
          (227, 119, 194), (127, 127, 127), (188, 189, 34), (23, 190, 207))

@@ -344,8 +344,18 @@ class ResnetBlock2D(nn.Module):
             # the residual add: neither is a separate pass over the activations
             # (3×3 convolutions: Winograd F(4×4, 3×3) where the shape fills the chip, else MIOpen)
             from .. import ops
-            y, x = gn_act_res(self.norm1, x, True)   # x goes on to the residual / shortcut
-            h = ops.conv3x3(y, self.conv1.weight)
+            # without gradient (the VAE encoder) the normalised activation has no other consumer:
+            # where the planner's measured table says so, GroupNorm + SiLU are applied inside the
+            # convolution's input-transform pass (ops.gn_conv3x3) and never stored
+            vst = (not torch.is_grad_enabled() and x.dtype == torch.float32 and _fused(x, self.norm1)
+                   and (self.dropout.p == 0 or not self.training))
+            K = self.conv1.out_channels
+            if vst and ops.gn_conv3x3_wins(x.shape[0], x.shape[1], K, x.shape[2], x.shape[3]):
+                n1 = self.norm1
+                h = ops.gn_conv3x3(x, n1.weight, n1.bias, n1.num_groups, n1.eps, True, None, self.conv1.weight)
+            else:
+                y, x = gn_act_res(self.norm1, x, True)   # x goes on to the residual / shortcut
+                h = ops.conv3x3(y, self.conv1.weight)
             shift = self.conv1.bias[None]
             if temb is not None and self.time_emb_proj is not None:
                 shift = shift + self.time_emb_proj(F.silu(temb))
@@ -357,6 +367,10 @@ class ResnetBlock2D(nn.Module):
                     bias = bias + self.conv_shortcut.bias
                 else:
                     x = self.conv_shortcut(x)
+            if vst and ops.gn_conv3x3_wins(h.shape[0], K, K, h.shape[2], h.shape[3]):
+                n2 = self.norm2
+                return ops.gn_conv3x3(h, n2.weight, n2.bias, n2.num_groups, n2.eps, True, shift, self.conv2.weight,
+                                      bias, x)
             return ops.conv3x3(self.dropout(gn_act(self.norm2, h, True, shift)), self.conv2.weight, bias, x)
         h = self.conv1(gn_act(self.norm1, x, True))
         if temb is not None and self.time_emb_proj is not None:
