@@ -398,13 +398,18 @@ int skp_conv3x3_wino2_gn(const float* x, const float* U, const float* bias, cons
  * workgroups: the V-staged pair for the frozen, gradient-free VAE encoder's GroupNorm → SiLU → 3×3
  * convolution (diffusers ResnetBlock2D inside Encoder, ptp_utils.py:289-304 image2latent).
  * skp_wino2_vtransform: V = Bᵀ d B of every 4×4 tile of d = x (B, C, H, W), zero padded; H, W
- *   multiples of 32, C % 4 == 0.  V holds B·C·H·W/16·40 floats: per half-height block (8 × 4 tiles,
- *   blocks in image, row, column order) and 4-channel stage one 20-KB slab [4 ch][32 tiles][40]
- *   whose rows are laid out as U's (positions 0..17 at 0..17, 18..35 at 20..37, zero pads).
+ *   multiples of 32, C % 4 == 0.  V holds B·C·H·W/16·36 floats, no padding: per half-height block
+ *   (8 × 4 tiles, blocks in image, row, column order) and 4-channel stage one 18-KB slab
+ *   [wave q][chunk j][lane L], lane-major for the wave that consumes it: q = 2·half + wm (half 0 /
+ *   1 = transform rows 0-2 / 3-5, i.e. positions 0..17 / 18..35; wm = tile rows 2wm, 2wm + 1 of the
+ *   block), lane L = (stage channel L >> 4, tile 16·wm + (L & 15) of the block's 32), and the
+ *   lane's 18 positions as chunks j = 0..3 of 16 B (64 lanes × 16 B = 1 KB each, positions
+ *   4j..4j + 3 of the half) and chunk 4 of 8 B (512 B, positions 16, 17): 4.5 KB per wave.
  * skp_wino2_vtransform_gn: the same with d = act(GroupNorm(x + shift)) computed on load from
  *   stats (B·G·2 floats (mean, rstd), from skp_groupnorm_stats / _stats_part or a forward),
  *   gamma, beta and shift (B·C floats or NULL): bit for bit the values skp_groupnorm_fwd writes,
- *   never stored; the padding is of d, not of x.  One pass: reads x, writes V (14 B per element).
+ *   never stored; the padding is of d, not of x.  One pass: reads x (4 B per element), writes V
+ *   (36 floats per 16 = 9 B per element); the convolution's first read of V is 9 B per element.
  * skp_conv3x3_wino2_v / _v_gn: skp_conv3x3_wino2 / _gn with V in place of x; same U, epilogues,
  *   nsplit / ws and gn_part, and the same bits as skp_conv3x3_wino2 on d at the same nsplit. */
 int skp_wino2_vtransform(const float* x, float* V, int B, int C, int H, int W, void* stream);

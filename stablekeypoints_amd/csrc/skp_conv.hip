@@ -544,6 +544,11 @@ constexpr int kUP = 40;                    // floats per (input, output channel)
 constexpr int kUF = kCK * kNC * kUP;       // 5120 floats = 20 KB per U slot
 constexpr int kUInstr = kUF / 256;         // 20
 constexpr unsigned kOOB = 0x80000000u;     // buffer offset past any num_records (< 2 GiB): loads 0
+// V of the V-staged form: per (half-height block, stage) a slab [wave 2HH + wm][chunk j][lane] of
+// the lanes' A operands a[18] — four 16-B chunks (1 KB per wave) and one 8-B chunk (512 B)
+constexpr int kVWF = 4 * 256 + 128;        // 1152 floats = 4.5 KB per wave
+constexpr int kVF = 4 * kVWF;              // 4608 floats = 18 KB per slab (36 per tile and channel)
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 static_assert(kUF % 256 == 0, "whole 1-KB chunks");
 static_assert((4 * GeoT<8>::RAWF + 3 * kUF) * 4 <= 160 * 1024 && 3 * (GeoT<4>::RAWF + kUF) * 4 <= 160 * 1024, "LDS");
 static_assert(2 * 8 * 1024 <= kUF * 4, "epilogue exchange: two waves' 8 KB per ring buffer");
@@ -739,10 +744,13 @@ __device__ __forceinline__ void w2_vmcnt(int n) {
 // on the wave's half so the stage loop is straight-line code for each.
 //
 // VST (the V-staged form, skp_conv3x3_wino2_v): `x` is not the image but its transform V from
-// skp_wino2_vtransform, one 20-KB slab [4 ch][32 tiles][40] per (half-height block, stage) in
-// U's row layout.  The raw ring and the per-lane transform are replaced by a V ring (sm.R0, sm.R1)
-// filled by LDS-DMA like U; the A operand is read from LDS per stage with the B operand's row
-// pattern.  MFMA order, accumulators and the epilogue are the same code.
+// skp_wino2_vtransform, one 18-KB slab [wave][chunk][lane] per (half-height block, stage): lane L
+// of wave wv finds its own a[18] there, written by lane L of wave wv of the transform pass.  LDS
+// would give V no reuse (every element goes to one lane of one wave), so the raw ring and the
+// per-lane transform are replaced by buffer loads straight into a ring of three A-operand register
+// buffers, two stages ahead of use; the LDS that frees lets U's ring be three slots deep as well
+// (60 KB: still two workgroups per CU).  sm.R0 / sm.R1 are only the epilogue's plane buffers here,
+// carved from the U ring.  MFMA order, accumulators and the epilogue are the same code.
 template <int EPI, int HH, int TXB, int NW, bool VST = false>
 __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __restrict__ x, const float* __restrict__ U,
                                            const float* __restrict__ bias, const float* __restrict__ res,
@@ -864,20 +872,34 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   };
 
   if constexpr (VST) {
-    // slab of (tile block, stage t): V + ((tb · C/4) + c0/4 + t) · kUF; 20 chunks of 1 KB, 5 per wave
+    // slab of (tile block, stage t): V + ((tb · C/4) + c0/4 + t) · kVF; wave wv's 4.5 KB of it is
+    // [chunk j][lane]: four 16-B chunks and one 8-B chunk per lane = that lane's a[18]
+    using w2::kVF;
+    using w2::kVWF;
     const int bw = W >> 5;
     const size_t tb = (size_t)img * ((H >> 4) * bw) + (size_t)(y0 >> 4) * bw + (x0 >> 5);
-    const float* Vb = x + (tb * (size_t)(C / w2::kCK) + (size_t)(c0 / w2::kCK)) * kUF;
-    auto issue_vu = [&](int t, float* vs_lds, float* us_lds) {
+    const float* Vb = x + (tb * (size_t)(C / w2::kCK) + (size_t)(c0 / w2::kCK)) * kVF + wv * kVWF;
+    // V is a read-only __restrict__ argument, whose loads the compiler may move anywhere, across
+    // barriers and the memory fences below too; the explicit vmcnt allowance counts on every
+    // stage's loads staying in the step that issues them, so the pointer is made opaque
+    asm volatile("" : "+s"(Vb));
+    struct AReg {
+      u32x4 c[4];
+      w2::u32x2 d;
+    };
+    // V(t) → registers, U(t) → LDS slot t % 3: five buffer loads and five DMAs per wave, issued
+    // whether or not stage t exists (past the last stage both resources are zero-length: nothing
+    // is fetched and the in-order vmcnt counts stay the same every stage)
+    auto issue_vu = [&](int t, AReg& an, float* us_lds) {
+      const bool ok = t < nst;
+      const size_t tt = ok ? (size_t)t : 0;
       const __amdgpu_buffer_rsrc_t rv =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(Vb + (size_t)t * kUF), (short)0, kUF * 4, 0x00020000);
+          __builtin_amdgcn_make_buffer_rsrc((void*)(Vb + tt * kVF), (short)0, ok ? kVWF * 4 : 0, 0x00020000);
       const __amdgpu_buffer_rsrc_t ru =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(Ub + (size_t)t * kUF), (short)0, kUF * 4, 0x00020000);
+          __builtin_amdgcn_make_buffer_rsrc((void*)(Ub + tt * kUF), (short)0, ok ? kUF * 4 : 0, 0x00020000);
 #pragma unroll
-      for (int m = 0; m < w2::kUInstr / NW; ++m) {
-        const int q = wv + NW * m;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(vs_lds + 256 * q), 16, lane * 16, q * 1024, 0, 0);
-      }
+      for (int j = 0; j < 4; ++j) an.c[j] = __builtin_amdgcn_raw_buffer_load_b128(rv, lane * 16, j * 1024, 0);
+      an.d = __builtin_amdgcn_raw_buffer_load_b64(rv, lane * 8, 4096, 0);
 #pragma unroll
       for (int m = 0; m < w2::kUInstr / NW; ++m) {
         const int q = wv + NW * m;
@@ -885,33 +907,53 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
       }
     };
     static_assert(w2::kUInstr % NW == 0, "whole chunks per wave");
-    // A operand: V[kc][16 wm + (lane & 15)][18 HH + q], the row pattern of the B operand
-    const int aoff = (kc * 32 + 16 * wm + (lane & 15)) * kUP + 20 * HH;
-    // stage s: wait for V(s), U(s); barrier (everyone is past stage s−1, whose slots are free);
-    // issue V(s+1), U(s+1) into them; read the A operand and run the MFMAs on slot s % 2
-    auto vstep = [&](int s, const float* Vs, const float* Us, float* Vi, float* Ui) {
-      W2_VMCNT(0);
-      __syncthreads();
-      if (s + 1 < nst) issue_vu(s + 1, Vi, Ui);
-      float a[18];
-      const float* vb = Vs + aoff;
+    constexpr int kPerStage = 5 + w2::kUInstr / NW;   // vector-memory instructions per wave and stage
+    // stage s: wait for this wave's U(s) DMAs (everything but the kPerStage instructions of V(s+1),
+    // U(s+1) — V(s) precedes U(s) in the in-order counter); barrier (every wave's U(s) has landed and
+    // everyone is past stage s−1, whose U slot is free); issue V(s+2), U(s+2); MFMAs on A(s), slot s % 3
+    // The loads are ordinary (compiler-counted) buffer loads.  Each step uses A(s) unconditionally
+    // (the empty asm) in a block every path runs through, so the loads can be neither sunk into a
+    // conditional block nor waited for with anything but a counted vmcnt, which the step's own
+    // explicit one already covers; only the MFMAs of a step past the last stage are skipped.
+    auto vstep = [&](int s, const AReg& ac, const float* Us, AReg& ai, float* Ui) {
+      // A bare s_barrier between compiler-only memory fences, not __syncthreads(): its release
+      // fence waits vmcnt(0) for the DMAs in flight and would take the lead back to one stage.
+      // This wave's LDS reads of stage s−1 have returned (lgkmcnt(0)) before it signals.
+      W2_VMCNT(kPerStage);
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) alone
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      asm volatile("" ::"v"(ac.c[0]), "v"(ac.c[1]), "v"(ac.c[2]), "v"(ac.c[3]), "v"(ac.d));
+      issue_vu(s + 2, ai, Ui);
+      __builtin_amdgcn_sched_barrier(0);   // the loads stay ahead of the stage's MFMAs
+      if (s < nst) {
+        float a[18];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float4 v = *reinterpret_cast<const float4*>(vb + 4 * j);
-        a[4 * j] = v.x;
-        a[4 * j + 1] = v.y;
-        a[4 * j + 2] = v.z;
-        a[4 * j + 3] = v.w;
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const unsigned v = ac.c[j][i];   // by value: a bit_cast of the element lvalue reads element 0
+            a[4 * j + i] = __uint_as_float(v);
+          }
+        const unsigned d0 = ac.d[0], d1 = ac.d[1];
+        a[16] = __uint_as_float(d0);
+        a[17] = __uint_as_float(d1);
+        mfmas(Us, a);
       }
-      const float2 v2 = *reinterpret_cast<const float2*>(vb + 16);
-      a[16] = v2.x;
-      a[17] = v2.y;
-      mfmas(Us, a);
     };
-    issue_vu(0, R0, U0);
-    for (int s0 = 0; s0 < nst; s0 += 2) {
-      vstep(s0, R0, U0, R1, U1);
-      if (s0 + 1 < nst) vstep(s0 + 1, R1, U1, R0, U0);
+    // A-operand ring of three register buffers and U ring of three LDS slots: lead 2, the loop
+    // unrolled by the ring period.  With fewer stages than the lead, and in the steps that round
+    // the stage count up to the period, the extra issues are the empty ones above.
+    AReg A0, A1, A2;
+    issue_vu(0, A0, U0);
+    asm volatile("" ::: "memory");   // stage 0's instructions stay ahead of stage 1's in the counter
+    __builtin_amdgcn_sched_barrier(0);
+    issue_vu(1, A1, U1);
+    for (int s0 = 0; s0 < nst; s0 += 3) {
+      vstep(s0, A0, U0, A2, U2);
+      vstep(s0 + 1, A1, U1, A0, U0);
+      vstep(s0 + 2, A2, U2, A1, U1);
     }
   } else {
     // prologue: the DMAs of "steps" −RS..−1 (raw(0..RS−1), U(0), U(1)) in step order; wait for
@@ -1200,15 +1242,18 @@ __global__ void wino2_weights_kernel(const float* __restrict__ w, int K, int C, 
     }
 }
 
-// The V-staged form of wino2_kernel<EPI, 8, 4>: half-height blocks, 4 waves, a two-slot V ring and a
-// two-slot U ring of 20 KB each (80 KB: two workgroups per CU); grid order as wino2_kernel.
+// The V-staged form of wino2_kernel<EPI, 8, 4>: half-height blocks, 4 waves, V in registers and a
+// three-slot U ring of 20 KB each (60 KB: two workgroups per CU); grid order as wino2_kernel.
 template <int EPI>
 __global__ __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino2v_kernel(
     const float* __restrict__ V, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ res, float* __restrict__ y, int nimg, int C, int K, int H, int W, int bw, int bpi,
     int nblk, int nkb, int kb_major, int csplit, int dbg, float2* __restrict__ gnp) {
-  __shared__ __attribute__((aligned(16))) float V0[w2::kUF], V1[w2::kUF], U0[w2::kUF], U1[w2::kUF];
-  static_assert(4 * w2::kUF * 4 <= 80 * 1024, "two workgroups per CU");
+  __shared__ __attribute__((aligned(16))) float U0[w2::kUF], U1[w2::kUF], U2[w2::kUF];
+  static_assert(3 * w2::kUF * 4 <= 80 * 1024, "two workgroups per CU");
+  // the epilogue's four plane buffers (4 planes of 16 × 32 + 4 floats, skewed by up to 48): the
+  // halves of U0 and U1
+  static_assert(4 * (16 * 32 + 4) + 48 <= w2::kUF / 2, "a plane buffer per half U slot");
   const int G = gridDim.x;
   const int g = blockIdx.x;
   const int Lg = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
@@ -1228,7 +1273,7 @@ __global__ __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))
   const int by = br / bw;
   const int x0 = 32 * (br - by * bw), y0 = 16 * by;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const W2Smem sm{V0, V1, nullptr, nullptr, U0, U1, nullptr};
+  const W2Smem sm{U0 + w2::kUF / 2, U1 + w2::kUF / 2, nullptr, nullptr, U0, U1, U2};
   const int c0 = sp * csplit;
   if (wv < 2)
     wino2_body<EPI, 0, 8, 4, true>(sm, V, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
@@ -1239,8 +1284,9 @@ __global__ __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))
 // zero padding applied to d.  One workgroup per (half-height block of 8 × 4 tiles, 4-channel
 // stage): the 18 × 40-float region rows of the 4 channels go through LDS in wino2_kernel's raw-slot
 // layout (so the patch reads and the transform are that kernel's, bit for bit), each wave
-// transforms one half (rows 3HH..3HH+2) of 16 tiles × 4 channels, and the 20-KB slab
-// [4 ch][32 tiles][40] leaves through LDS as 1-KB wave stores.
+// transforms one half (rows 3HH..3HH+2) of 16 tiles × 4 channels, and each lane stores its a[18]
+// straight from registers into the 18-KB slab [wave][chunk][lane] (coalesced wave stores), where
+// the same lane of the same wave of wino2v_kernel loads it.
 // GN: 0 plain, 1 GroupNorm, 2 GroupNorm + SiLU.
 template <int GN>
 __global__ __launch_bounds__(4 * WAVE) void wino2_vtransform_kernel(
@@ -1250,7 +1296,6 @@ __global__ __launch_bounds__(4 * WAVE) void wino2_vtransform_kernel(
   using Geo = w2::GeoT<8, 4>;
   constexpr int RR = Geo::RR, RC = Geo::RC, kChF = Geo::CHF, kRowF = Geo::RF;
   __shared__ __attribute__((aligned(16))) float R[Geo::RAWF];
-  __shared__ __attribute__((aligned(16))) float O[w2::kUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int nst = C / w2::kCK;
   const int tb = blockIdx.x / nst, st = blockIdx.x - tb * nst;
@@ -1283,19 +1328,15 @@ __global__ __launch_bounds__(4 * WAVE) void wino2_vtransform_kernel(
   const int HH = wv >> 1, wm = wv & 1;
   const int kc = lane >> 4, tx = lane & 7, ty = 2 * wm + ((lane >> 3) & 1);
   const int roff = kc * kChF + 4 * ty * kRowF + 4 * tx;
-  float a[20];
+  float a[18];
   if (HH == 0) w2::W2_TRANSFORM<0, kRowF>(R + roff, a);
   else w2::W2_TRANSFORM<1, kRowF>(R + roff, a);
-  a[18] = a[19] = 0.0f;   // the row's pads, as in U
-  float* o = O + (kc * 32 + 16 * wm + (lane & 15)) * w2::kUP + 20 * HH;
+  // the lane's a[18] as wave stores of 1 KB (four) and 512 B (one) into the wave's [chunk][lane] part
+  float* o = V + (size_t)blockIdx.x * w2::kVF + wv * w2::kVWF;
 #pragma unroll
-  for (int j = 0; j < 5; ++j)
-    *reinterpret_cast<float4*>(o + 4 * j) = make_float4(a[4 * j], a[4 * j + 1], a[4 * j + 2], a[4 * j + 3]);
-  __syncthreads();
-  float4* out = reinterpret_cast<float4*>(V + (size_t)blockIdx.x * w2::kUF);
-#pragma unroll
-  for (int i = 0; i < w2::kUF / 4 / (4 * WAVE); ++i)
-    out[i * 4 * WAVE + tid] = reinterpret_cast<const float4*>(O)[i * 4 * WAVE + tid];
+  for (int j = 0; j < 4; ++j)
+    *reinterpret_cast<float4*>(o + 256 * j + 4 * lane) = make_float4(a[4 * j], a[4 * j + 1], a[4 * j + 2], a[4 * j + 3]);
+  *reinterpret_cast<float2*>(o + 1024 + 2 * lane) = make_float2(a[16], a[17]);
 }
 
 }  // namespace
@@ -1419,11 +1460,15 @@ extern "C" int skp_conv3x3_wino2(const float* x, const float* U, const float* bi
 
 // ---------------------------------------------------------------- V-staged form (transform once)
 // skp_wino2_vtransform(_gn) writes V = Bᵀ d B of every input tile once; skp_conv3x3_wino2_v(_gn)
-// is skp_conv3x3_wino2(_gn) reading V instead of x.  Bytes model of the transform pass at
-// (B, C, H, W): reads x once from HBM (4 B per element; the halo rows / columns of a block, 1.4×
-// the block in all, come from L2) and writes 40 floats per 4×4 tile (10 B per element): 14 B per
-// element against the 8 B of the gn_apply pass it replaces; the convolution then fetches 10 B per
-// element once from HBM (its other K/32 − 1 reads hit L2) instead of 4.
+// is skp_conv3x3_wino2(_gn) reading V instead of x.  V layout (include/skp.h): per (half-height
+// block, 4-channel stage) one 18-KB slab [wave 2·half + wm][chunk j][lane], each lane's a[18] as
+// four 16-B chunks and one 8-B chunk, so that a wave stores / loads whole contiguous 1-KB (512-B)
+// pieces and lane L of wave q reads exactly what lane L of wave q wrote; no pad floats.  Bytes
+// model of the transform pass at (B, C, H, W): reads x once from HBM (4 B per element; the halo
+// rows / columns of a block, 1.4× the block in all, come from L2) and writes 36 floats per 4×4
+// tile (9 B per element): 4 + 9 = 13 B per element against the 8 B of the gn_apply pass it
+// replaces; the convolution then fetches 9 B per element once from HBM (its other K/32 − 1 reads
+// hit L2) instead of 4.
 namespace {
 int vtransform_launch(const float* x, const float* stats, const float* gamma, const float* beta, const float* shift,
                       int G, int act, float* V, int B, int C, int H, int W, void* stream) {

@@ -1932,13 +1932,15 @@ def conv3x3(x, weight, bias=None, residual=None):
 # measured (tools/wino_time.py --pair, batch 8, each side in a process of its own): a
 # (C, K, H, W) is listed only where the new pair beat gn_apply + wino2 by more than the spread
 # of its own repeats.  Tests add entries to force the path.
-#   (C, K, H, W)          old pair µs  new pair µs   (profiles/r07a_vst_pair_ab.txt, medians of 3)
-#   512→512 @ 64²            606.4        547.1   +9.8%
-#   256→512 @ 128²          1223.9       1101.2  +10.0%
-#   512→512 @ 128²          2205.6       1903.5  +13.7%
-#   128→256 @ 256²          1381.3       1338.6   +3.1%
-#   256→256 @ 256²          2355.3       2241.6   +4.8%
-#   128→128 @ 512²          2698.2       2915.0   −8.0%   stays on wino2: V's extra HBM traffic outweighs it
+#   (C, K, H, W)          old pair µs  new pair µs   (profiles/r08a_vst_pair_ab.txt, medians of 3)
+#   512→512 @ 64²            592.1        505.6  +14.6%
+#   256→512 @ 128²          1203.4       1034.8  +14.0%
+#   512→512 @ 128²          2165.3       1767.0  +18.4%
+#   128→256 @ 256²          1376.3       1239.1  +10.0%
+#   256→256 @ 256²          2319.7       2062.9  +11.1%
+#   128→128 @ 512²          2716.3       2615.1   +3.7%   not listed: the pair wins in isolation, but in the bench
+#       step its 2.4 GB of V cost the layers after it more than that (88.898 ms per step without the entry,
+#       89.014 with it, every repeat; profiles/r08a_vst_pair_ab.txt)
 WINO_V_SHAPES = {(512, 512, 64, 64), (256, 512, 128, 128), (512, 512, 128, 128), (128, 256, 256, 256),
                  (256, 256, 256, 256)}
 WINO_V_MIN_BATCH = 4   # the table was measured at batch 8: grids of at least half that size
@@ -1984,7 +1986,7 @@ def gn_conv3x3(x, gamma, beta, groups, eps, act, shift, weight, bias=None, resid
     else:
         call("skp_groupnorm_stats", ptr(x), ptr(shift), B, C, H * W, int(groups), float(eps), ptr(stats), ptr(part),
              stream(dev))
-    V = torch.empty(B * C * (H // 4) * (W // 4) * 40, device=dev, dtype=F32)
+    V = torch.empty(B * C * (H // 4) * (W // 4) * 36, device=dev, dtype=F32)
     with _timed("skp_wino2_vtransform_gn", 0):
         call("skp_wino2_vtransform_gn", ptr(x), ptr(stats), ptr(g), ptr(b), ptr(shift), int(groups), int(bool(act)),
              ptr(V), B, C, H, W, stream(dev))
