@@ -421,12 +421,19 @@ int skp_conv3x3_wino2_v_gn(const float* V, const float* U, const float* bias, co
                            int C, int K, int H, int W, int nsplit, float* ws, float* gn_part, void* stream);
 /* diffusers' Downsample2D(padding=0) of the VAE encoder (F.pad(x, (0, 1, 0, 1)) then a 3×3 stride-2
  * convolution; the encoder behind ptp_utils.image2latent, reference ptp_utils.py:289-304):
- * y (B, K, H/2, W/2) = the stride-1 pad-1 convolution of x sampled at (2oy + 1, 2ox + 1), + bias,
- * computed by the skp_conv3x3_wino2 kernel (U from skp_wino2_weights) with a stride-2 epilogue.
- * H, W multiples of 32; C % 4 == 0, K % 32 == 0; nsplit as skp_conv3x3_wino2 (workspace
- * nsplit·B·K·(H/2)·(W/2) floats).                                                              */
-int skp_conv3x3s2_wino2(const float* x, const float* U, const float* bias, float* y, int B, int C, int K, int H,
-                        int W, int nsplit, float* ws, void* stream);
+ * y (B, K, H/2, W/2), + bias, in the stride-2 minimal-product form: 2×2 output tiles (input pitch 4,
+ * the 5×5 sub-patch of rows / columns 1..5 of skp_conv3x3_wino2's 6×6 patch) from 25 products, against
+ * 36 per 4 kept outputs for the stride-1 kernel sampled at the odd positions; every input-transform
+ * coefficient is 0 or ±1.
+ *   V = Bs2ᵀ d Bs2, U = Gs2 g Gs2ᵀ, Y = As2ᵀ (Σc U ⊙ V) As2 with
+ *   Bs2ᵀ = [1 0 −1 0 0; 0 0 1 0 0; 0 0 1 0 −1; 0 1 0 0 0; 0 0 0 1 0], Gs2 = [1 0 0; 1 0 1; 0 0 1; 0 1 0; 0 1 0],
+ *   As2ᵀ = [1 1 0 1 0; 0 1 −1 0 1].
+ * skp_wino2s2_weights writes U (fp64 → fp32) as [K/32][C][32][28]: positions 5i + j of rows i = 0..2
+ * at 0..14, of rows 3..4 at 16..25, zero pads.  skp_conv3x3s2_f2: H, W multiples of 32; C % 4 == 0,
+ * K % 32 == 0; nsplit as skp_conv3x3_wino2 (workspace nsplit·B·K·(H/2)·(W/2) floats).            */
+int skp_wino2s2_weights(const float* w, int K, int C, float* U, void* stream);
+int skp_conv3x3s2_f2(const float* x, const float* U, const float* bias, float* y, int B, int C, int K, int H, int W,
+                     int nsplit, float* ws, void* stream);
 
 /* ---------------------------------------------------------------- A17 visualisation sheets
  * Per-map (min, max) for the heat overlay: the normalisation of visualize.py:60-61

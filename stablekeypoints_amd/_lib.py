@@ -95,7 +95,8 @@ _SIGS = {
     "skp_wino2_vtransform_gn": [_p, _p, _p, _p, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _p],
     "skp_conv3x3_wino2_v": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p],
     "skp_conv3x3_wino2_v_gn": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p],
-    "skp_conv3x3s2_wino2":[_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p],
+    "skp_wino2s2_weights": [_p, _c_int, _c_int, _p, _p],
+    "skp_conv3x3s2_f2":   [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p],
     "skp_map_range": [_p, _c_int, _c_int, _c_int, _p, _p],
     "skp_render_sheet": [_p, _c_int, _c_int, _c_int, _p, _c_int, _c_int, _p, _p, _c_float, _p, _c_int, _c_float, _p,
                          _c_int, _c_int, _c_int, _c_int, _p, _p],

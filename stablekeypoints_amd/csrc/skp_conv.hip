@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     kb = L - tb * nkb;
   }
   const int c0 = sp * csplit;
-  y += (size_t)sp * nimg * K * ((EPI & 4) ? (H / 2) * (W / 2) : H * W);   // EPI bit 2: stride-2 output
+  y += (size_t)sp * nimg * K * H * W;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -548,8 +548,12 @@ constexpr unsigned kOOB = 0x80000000u;     // buffer offset past any num_records
 // the lanes' A operands a[18] — four 16-B chunks (1 KB per wave) and one 8-B chunk (512 B)
 constexpr int kVWF = 4 * 256 + 128;        // 1152 floats = 4.5 KB per wave
 constexpr int kVF = 4 * kVWF;              // 4608 floats = 18 KB per slab (36 per tile and channel)
+// the stride-2 form (S2): 25 positions per (input, output channel), transform rows 0-2 at 0..14 and
+// rows 3-4 at 16..25 of a 28-float row (16-B aligned halves; 28·lane mod 64 banks are distinct)
+constexpr int kUP2 = 28;
+constexpr int kUF2 = kCK * kNC * kUP2;     // 3584 floats = 14 KB per U slot
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-static_assert(kUF % 256 == 0, "whole 1-KB chunks");
+static_assert(kUF % 256 == 0 && kUF2 % 256 == 0, "whole 1-KB chunks");
 static_assert((4 * GeoT<8>::RAWF + 3 * kUF) * 4 <= 160 * 1024 && 3 * (GeoT<4>::RAWF + kUF) * 4 <= 160 * 1024, "LDS");
 static_assert(2 * 8 * 1024 <= kUF * 4, "epilogue exchange: two waves' 8 KB per ring buffer");
 
@@ -707,6 +711,60 @@ __device__ __forceinline__ void half_output(const float* m, float* y) {
     }
 }
 
+// The stride-2 form: F.pad(x, (0, 1, 0, 1)) then a 3×3 / stride-2 convolution as 2×2 output tiles
+// of 25 products.  In one dimension two outputs read d0..d4 = rows / columns 1..5 of the 6×6
+// patch: (d0 − d2)g0, d2(g0 + g2), (d2 − d4)g2 (F(2, 2) on the even inputs) and d1 g1, d3 g1:
+//   Bs2ᵀ = [1 0 −1 0 0; 0 0 1 0 0; 0 0 1 0 −1; 0 1 0 0 0; 0 0 0 1 0],  As2ᵀ = [1 1 0 1 0; 0 1 −1 0 1].
+// Half H = 0 holds transform rows 0-2 (the even patch rows, 15 positions), H = 1 rows 3-4 (the
+// odd ones, 10 positions): a[5 ii + j] = V[3H + ii][j].  Two ds_read_b128 per patch row.
+template <int H, int RF>
+__device__ __forceinline__ void s2_transform(const float* raw, float* a) {
+  constexpr int NR = H ? 2 : 3;
+  float d[NR][5];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const float* rp = raw + (H ? 2 + 2 * i : 1 + 2 * i) * RF;
+    const float4 c1 = *reinterpret_cast<const float4*>(rp + 4);
+    const float4 c2 = *reinterpret_cast<const float4*>(rp + 8);
+    d[i][0] = c1.x;
+    d[i][1] = c1.y;
+    d[i][2] = c1.z;
+    d[i][3] = c1.w;
+    d[i][4] = c2.x;
+    // keep chunk 2 whole (see half_transform)
+    asm volatile("" ::"v"(c2.y), "v"(c2.z), "v"(c2.w));
+  }
+#pragma unroll
+  for (int ii = 0; ii < NR; ++ii) {
+    float t[5];
+#pragma unroll
+    for (int b = 0; b < 5; ++b)
+      t[b] = H ? d[ii][b] : ii == 0 ? d[0][b] - d[1][b] : ii == 1 ? d[1][b] : d[1][b] - d[2][b];
+    a[5 * ii] = t[0] - t[2];
+    a[5 * ii + 1] = t[2];
+    a[5 * ii + 2] = t[2] - t[4];
+    a[5 * ii + 3] = t[1];
+    a[5 * ii + 4] = t[3];
+  }
+}
+
+// partial 2×2 output tile of half H's rows of M (m[5 ii + j] = M[3H + ii][j]) → y[4] (row-major)
+template <int H>
+__device__ __forceinline__ void s2_output(const float* m, float* y) {
+  constexpr int NR = H ? 2 : 3;
+  float s[NR][2];
+#pragma unroll
+  for (int ii = 0; ii < NR; ++ii) {
+    s[ii][0] = (m[5 * ii] + m[5 * ii + 1]) + m[5 * ii + 3];
+    s[ii][1] = (m[5 * ii + 1] - m[5 * ii + 2]) + m[5 * ii + 4];
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    y[c] = H ? s[0][c] : s[0][c] + s[1][c];
+    y[2 + c] = H ? s[1][c] : s[1][c] - s[NR - 1][c];
+  }
+}
+
 }  // namespace w2
 
 struct W2Smem {
@@ -751,7 +809,11 @@ __device__ __forceinline__ void w2_vmcnt(int n) {
 // buffers, two stages ahead of use; the LDS that frees lets U's ring be three slots deep as well
 // (60 KB: still two workgroups per CU).  sm.R0 / sm.R1 are only the epilogue's plane buffers here,
 // carved from the U ring.  MFMA order, accumulators and the epilogue are the same code.
-template <int EPI, int HH, int TXB, int NW, bool VST = false>
+//
+// S2 (the stride-2 form, skp_conv3x3s2_f2): the same staging, rings and barriers; each tile's 5×5
+// sub-patch gives a 2×2 tile of the (H/2, W/2) output from 25 products (s2_transform above), U
+// rows are 28 floats (14 KB per slot) and the epilogue exchanges 8 × 16-pixel planes.
+template <int EPI, int HH, int TXB, int NW, bool VST = false, bool S2 = false>
 __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __restrict__ x, const float* __restrict__ U,
                                            const float* __restrict__ bias, const float* __restrict__ res,
                                            float* __restrict__ y, int C, int K, int H, int W, int img, int x0,
@@ -760,15 +822,16 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   using Geo = w2::GeoT<TXB, NW>;
   constexpr int kChF = Geo::CHF, kRowF = Geo::RF, kRawInstr = Geo::RAW_INSTR, NI = Geo::NI, RR = Geo::RR,
                 RC = Geo::RC;
-  constexpr int kInstr = kRawInstr + w2::kUInstr;
+  static_assert(!S2 || (TXB == 8 && NW == 4 && !VST && (EPI & ~1) == 0), "stride-2 form: half-height blocks, bias only");
+  constexpr int kUP = S2 ? w2::kUP2 : w2::kUP, kUF = S2 ? w2::kUF2 : w2::kUF, kUInstr = kUF / 256;
+  constexpr int NP = S2 ? (HH ? 10 : 15) : 18;   // positions of this half
+  constexpr int kInstr = kRawInstr + kUInstr;
   constexpr int kMaxRaw = (kRawInstr + NW - 1) / NW;
-  constexpr int kMaxU = (w2::kUInstr + NW - 1) / NW + 1;
+  constexpr int kMaxU = (kUInstr + NW - 1) / NW + 1;
   constexpr int NT = NW * WAVE;
   // weight ring: 3 slots (lead 2) with 8 waves; 2 (lead 1) in the half-height form, whose LDS must
   // leave room for a second workgroup on the CU
   constexpr int US = NW == 4 ? 2 : 3;
-  using w2::kUF;
-  using w2::kUP;
   // raw-input ring of RS slots (lead RS − 1 stages: the input streams from HBM), weight ring
   // of 3 (lead 2: the weights are re-read by every tile block and hit L2)
   static_assert(!VST || (TXB == 8 && NW == 4), "V-staged form: half-height blocks of 4 waves");
@@ -841,34 +904,43 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   const int ty = TXB == 8 ? 2 * wm + ((lane >> 3) & 1) : (lane >> 2) & 3;
   const int roff = kc * kChF + (TXB == 8 ? 0 : wm * RR * kRowF) + 4 * ty * kRowF + 4 * tx;
   // B operand: U[kc][16 blk + (lane & 15)][18 HH + q] (rows padded to 40, halves at 0 and 20)
-  const int uoff = (kc * w2::kNC + (lane & 15)) * kUP + 20 * HH;
+  // (S2: rows of 28, halves at 0 and 16)
+  const int uoff = (kc * w2::kNC + (lane & 15)) * kUP + (S2 ? 16 : 20) * HH;
 
-  f32x4 acc[2][18];
+  f32x4 acc[2][NP];
 #pragma unroll
   for (int b = 0; b < 2; ++b)
 #pragma unroll
-    for (int q = 0; q < 18; ++q) acc[b][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float a0[18], a1[18];   // A operands of the even / odd stages (no copies between stages)
+    for (int q = 0; q < NP; ++q) acc[b][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float a0[NP], a1[NP];   // A operands of the even / odd stages (no copies between stages)
 
-  auto mfmas = [&](const float* us, const float (&acur)[18]) {
+  auto mfmas = [&](const float* us, const float (&acur)[NP]) {
+    constexpr int N4 = (NP + 1) / 4;   // 18: 4 × 16 B + 8 B; 15: 4 × 16 B; 10: 2 × 16 B + 8 B
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       const float* ub = us + uoff + b * 16 * kUP;
-      float u[18];
+      float u[4 * N4 + 2];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < N4; ++j) {
         const float4 v = *reinterpret_cast<const float4*>(ub + 4 * j);
         u[4 * j] = v.x;
         u[4 * j + 1] = v.y;
         u[4 * j + 2] = v.z;
         u[4 * j + 3] = v.w;
       }
-      const float2 v2 = *reinterpret_cast<const float2*>(ub + 16);
-      u[16] = v2.x;
-      u[17] = v2.y;
+      if constexpr (NP % 4 == 2) {
+        const float2 v2 = *reinterpret_cast<const float2*>(ub + 4 * N4);
+        u[4 * N4] = v2.x;
+        u[4 * N4 + 1] = v2.y;
+      }
 #pragma unroll
-      for (int q = 0; q < 18; ++q) acc[b][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(acur[q], u[q], acc[b][q], 0, 0, 0);
+      for (int q = 0; q < NP; ++q) acc[b][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(acur[q], u[q], acc[b][q], 0, 0, 0);
     }
+  };
+  // the lane's patch of a raw slot → its A operands
+  auto transform = [&](const float* raw, float (&an)[NP]) {
+    if constexpr (S2) w2::s2_transform<HH, kRowF>(raw + roff, an);
+    else w2::W2_TRANSFORM<HH, kRowF>(raw + roff, an);
   };
 
   if constexpr (VST) {
@@ -966,23 +1038,23 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
     issue_raw(RS - 1, RS == 4 ? sm.R3 : RS == 3 ? R2 : R1);
     w2_vmcnt(nst > 1 ? allow_pro : 0);
     __syncthreads();
-    w2::W2_TRANSFORM<HH, kRowF>(R0 + roff, a0);
+    transform(R0, a0);
 
     // stage s: wait for U(s) and raw(s+1); barrier; issue U(s+2) and raw(s+RS) into the slots
     // freed by stage s-1; transform raw(s+1) (slot (s+1)%RS) and run the MFMAs on U(s) (slot
     // s%3).  The SIMD partners (waves w, w+4: the two halves) do these in opposite orders.
-    auto step = [&](int s, float* Rn, float* Us, float* Ri, float* Ui, const float (&acur)[18], float (&anext)[18]) {
+    auto step = [&](int s, float* Rn, float* Us, float* Ri, float* Ui, const float (&acur)[NP], float (&anext)[NP]) {
       w2_vmcnt(s + 1 < nst ? allow_step : 0);
       __syncthreads();
       if (s + US - 1 < nst) issue_u(s + US - 1, Ui);
       issue_raw(s + RS, Ri);   // past the last stage: empty (zero-length) loads keep the counts
       const bool tr = s + 1 < nst && !(dbg & 1);
       if (HH == 0) {
-        if (tr) w2::W2_TRANSFORM<HH, kRowF>(Rn + roff, anext);
+        if (tr) transform(Rn, anext);
         if (!(dbg & 2)) mfmas(Us, acur);
       } else {
         if (!(dbg & 2)) mfmas(Us, acur);
-        if (tr) w2::W2_TRANSFORM<HH, kRowF>(Rn + roff, anext);
+        if (tr) transform(Rn, anext);
       }
     };
     // unrolled by lcm(RS, 3, 2): raw slot s%RS, U slot s%3, A-operand buffer s%2
@@ -1009,166 +1081,201 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   W2_VMCNT(0);
   __syncthreads();
   if (dbg & 32) return;
-  // channel c of a block: a 32×32-float plane in R0/R1/R2/U0 (four channels each, skewed by 16
-  // floats per buffer so the 8-lane store groups hit distinct banks)
-  constexpr int PH = (TXB == 8 && NW == 4) ? 16 : 32;   // plane rows (TXB 8: the block's pixel rows)
-  // plane stride: TXB 8 the block's PH × 32 pixels, TXB 4 its NI 16×16 images (+4 skew); with a
-  // 2-slot raw ring the third plane buffer is U1 (no R2)
-  constexpr int PLS = (TXB == 8 ? PH * 32 : NI * 256) + 4;
-  float* const P2 = RS == 2 ? U1 : R2;
-  auto plane_of = [&](int c) -> float* {
-    float* b = (c >> 2) == 0 ? R0 : (c >> 2) == 1 ? R1 : (c >> 2) == 2 ? P2 : U0;
-    return b + (c & 3) * PLS + (c >> 2) * 16;
-  };
-  // this lane's output tile row within the 1024-float plane: TXB 8: tiles (2wm + lane>>5, 4((lane>>4)&1)
-  // + r) of the 32×32 block; TXB 4: image wm (256 floats), tile row lane>>4, tiles r = 0..3
-  float* pl = plane_of(lane & 15);
-  const int pbase = TXB == 8 ? (4 * (2 * wm + (lane >> 5))) * 32 + 4 * (4 * ((lane >> 4) & 1))
-                             : wm * 256 + (4 * (lane >> 4)) * 16;
-  constexpr int PW = TXB == 8 ? 32 : 16;   // plane row width
+  if constexpr (S2) {
+    // lane holds tiles (ty = 2wm + (lane>>5), tx = 4((lane>>4)&1) + r), r = 0..3, × channel 16 blk +
+    // (lane&15): its half's share of Y = As2ᵀ M As2, two output rows of 8 contiguous pixels.  Per
+    // block of 16 channels the other half's waves stage theirs in R0 as [ch][8 rows][16 px] planes
+    // (stride 132: the 16 channels of a store hit distinct banks), this half's add in place, then
+    // every thread stores two float4 of the (H/2, W/2) output.
+    constexpr int PLS2 = 8 * 16 + 4;
+    static_assert(16 * PLS2 <= Geo::RAWF, "stride-2 exchange planes fit one raw slot");
+    const int Ho = H / 2, Wo = W / 2;
+    float* pl = R0 + (lane & 15) * PLS2 + 2 * (2 * wm + (lane >> 5)) * 16 + 8 * ((lane >> 4) & 1);
 #pragma unroll
-  for (int blk = 0; blk < 2; ++blk) {
-    if (HH != blk) {
+    for (int blk = 0; blk < 2; ++blk) {
+      float o[4][4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float m[18], o[16];
+        float m[NP];
 #pragma unroll
-        for (int q = 0; q < 18; ++q) m[q] = acc[blk][q][r];
-        w2::half_output<HH>(m, o);
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-          *reinterpret_cast<float4*>(pl + pbase + f * PW + 4 * r) =
-              make_float4(o[4 * f], o[4 * f + 1], o[4 * f + 2], o[4 * f + 3]);
+        for (int q = 0; q < NP; ++q) m[q] = acc[blk][q][r];
+        w2::s2_output<HH>(m, o[r]);
       }
-    }
-    __syncthreads();
-    if (HH == blk) {
+      if (HH != blk) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float m[18], o[16];
+        for (int f = 0; f < 2; ++f)
 #pragma unroll
-        for (int q = 0; q < 18; ++q) m[q] = acc[blk][q][r];
-        w2::half_output<HH>(m, o);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          float4* d = reinterpret_cast<float4*>(pl + pbase + f * PW + 4 * r);
-          const float4 p = *d;
-          *d = make_float4(o[4 * f] + p.x, o[4 * f + 1] + p.y, o[4 * f + 2] + p.z, o[4 * f + 3] + p.w);
-        }
+          for (int h = 0; h < 2; ++h)
+            *reinterpret_cast<float4*>(pl + f * 16 + 4 * h) =
+                make_float4(o[2 * h][2 * f], o[2 * h][2 * f + 1], o[2 * h + 1][2 * f], o[2 * h + 1][2 * f + 1]);
       }
-    }
-    __syncthreads();
-    if constexpr ((EPI & 4) != 0) {
-      // stride-2 output (EPI bit 2, TXB 8): the block's odd rows / columns, a 16×16 block of the
-      // (H/2, W/2) output per channel = 16 channels × 64 float4, two per thread
-      static_assert(TXB == 8 && (EPI & 2) == 0, "stride-2 output: 32-wide blocks, no residual");
-      const int Ho = H / 2, Wo = W / 2;
-      constexpr int PC2 = (PH / 2) * 4;   // float4 per channel of the block's stride-2 output
+      __syncthreads();
+      if (HH == blk) {
 #pragma unroll
-      for (int i = 0; i < 16 * PC2 / NT; ++i) {
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            float4* d = reinterpret_cast<float4*>(pl + f * 16 + 4 * h);
+            const float4 p = *d;
+            *d = make_float4(o[2 * h][2 * f] + p.x, o[2 * h][2 * f + 1] + p.y, o[2 * h + 1][2 * f] + p.z,
+                             o[2 * h + 1][2 * f + 1] + p.w);
+          }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < 16 * 32 / NT; ++i) {
         const int idx = i * NT + tid;
-        const int c = idx / PC2, q = idx % PC2;
-        const int row = q >> 2, c4 = q & 3;
-        const float* pp = plane_of(c) + (2 * row + 1) * 32 + 8 * c4 + 1;
+        const int c = idx >> 5, row = (idx >> 2) & 7, c4 = idx & 3;
+        const float4 p = *reinterpret_cast<const float4*>(R0 + c * PLS2 + row * 16 + 4 * c4);
         const int k = kb * w2::kNC + 16 * blk + c;
         const float bv = (EPI & 1) ? bias[k] : 0.0f;
-        const size_t o = (((size_t)img * K + k) * Ho + y0 / 2 + row) * Wo + x0 / 2 + 4 * c4;
-        const float4 v = make_float4(pp[0] + bv, pp[2] + bv, pp[4] + bv, pp[6] + bv);
-        if (dbg & 128) __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(y + o));
-        else if (!(dbg & 64)) *reinterpret_cast<float4*>(y + o) = v;
+        const size_t o4 = (((size_t)img * K + k) * Ho + y0 / 2 + row) * Wo + x0 / 2 + 4 * c4;
+        const float4 v = make_float4(p.x + bv, p.y + bv, p.z + bv, p.w + bv);
+        if (dbg & 128) __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(y + o4));
+        else if (!(dbg & 64)) *reinterpret_cast<float4*>(y + o4) = v;
       }
       if (blk == 0) __syncthreads();
-      continue;
     }
-    // 16 channels × 1024 floats in 16-B chunks; a wave instruction = 1 KB of one channel:
-    // TXB 8: 8 whole rows of the 32×32 block; TXB 4: one whole 16×16 image plane
-    constexpr int PCF = TXB == 8 ? PH * 8 : NI * 64;   // float4 per channel plane
-    constexpr int NIT = 16 * PCF / NT;                  // wave instructions per wave
-    // TXB 8: wave w takes wave instructions 8w … 8w + 7 (1 KB = 8 rows of one channel each), so
-    // each consecutive pair is one 16-row × 32-pixel segment of one channel: the GroupNorm
-    // statistics below accumulate a pair in registers and reduce the wave's 4 segments together
-    static_assert(TXB != 8 || NIT == 8, "TXB 8: eight wave instructions per wave");
-    // (Σd, Σd²) of d = v − p around a pivot p per segment (a value of the segment: its first wave
-    // instruction's lane-0 x), so a channel whose mean is far from 0 relative to its spread loses
-    // nothing to cancellation; the segment leaves as (mean, M2) for Chan's combine (r05)
-    float g1[4] = {0.f, 0.f, 0.f, 0.f}, g2[4] = {0.f, 0.f, 0.f, 0.f}, piv[4] = {0.f, 0.f, 0.f, 0.f};
+  } else {
+    // channel c of a block: a 32×32-float plane in R0/R1/R2/U0 (four channels each, skewed by 16
+    // floats per buffer so the 8-lane store groups hit distinct banks)
+    constexpr int PH = (TXB == 8 && NW == 4) ? 16 : 32;   // plane rows (TXB 8: the block's pixel rows)
+    // plane stride: TXB 8 the block's PH × 32 pixels, TXB 4 its NI 16×16 images (+4 skew); with a
+    // 2-slot raw ring the third plane buffer is U1 (no R2)
+    constexpr int PLS = (TXB == 8 ? PH * 32 : NI * 256) + 4;
+    float* const P2 = RS == 2 ? U1 : R2;
+    auto plane_of = [&](int c) -> float* {
+      float* b = (c >> 2) == 0 ? R0 : (c >> 2) == 1 ? R1 : (c >> 2) == 2 ? P2 : U0;
+      return b + (c & 3) * PLS + (c >> 2) * 16;
+    };
+    // this lane's output tile row within the 1024-float plane: TXB 8: tiles (2wm + lane>>5, 4((lane>>4)&1)
+    // + r) of the 32×32 block; TXB 4: image wm (256 floats), tile row lane>>4, tiles r = 0..3
+    float* pl = plane_of(lane & 15);
+    const int pbase = TXB == 8 ? (4 * (2 * wm + (lane >> 5))) * 32 + 4 * (4 * ((lane >> 4) & 1))
+                               : wm * 256 + (4 * (lane >> 4)) * 16;
+    constexpr int PW = TXB == 8 ? 32 : 16;   // plane row width
 #pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int idx = TXB == 8 ? (((tid >> 6) * NIT + i) << 6) + (tid & 63) : i * NT + tid;
-      const int c = idx / PCF, q = idx % PCF;
-      const float4 v0 = *reinterpret_cast<const float4*>(plane_of(c) + 4 * q);
-      const int k = kb * w2::kNC + 16 * blk + c;
-      const float bv = (EPI & 1) ? bias[k] : 0.0f;
-      size_t o;
-      if (TXB == 8) {
-        const int row = q >> 3, c4 = q & 7;
-        o = (((size_t)img * K + k) * H + y0 + row) * W + x0 + 4 * c4;
-      } else {
-        o = ((size_t)(img + (q >> 6)) * K + k) * 256 + 4 * (q & 63);
-      }
-      float4 v = make_float4(v0.x + bv, v0.y + bv, v0.z + bv, v0.w + bv);
-      if (EPI & 2) {
-        const float4 rv = *reinterpret_cast<const float4*>(res + o);
-        v.x += rv.x;
-        v.y += rv.y;
-        v.z += rv.z;
-        v.w += rv.w;
-      }
-      if (dbg & 128) __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(y + o));
-      else if (!(dbg & 64)) *reinterpret_cast<float4*>(y + o) = v;
-      if (TXB == 8 && gnp) {   // the next GroupNorm's statistics: this lane's share of (Σd, Σd²)
-        if ((i & 1) == 0) piv[i >> 1] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v.x)));
-        const float p = piv[i >> 1];
-        const float dx = v.x - p, dy = v.y - p, dz = v.z - p, dw = v.w - p;
-        g1[i >> 1] += (dx + dy) + (dz + dw);
-        g2[i >> 1] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-    }
-    if (TXB == 8 && gnp) {
-      // Reduce the wave's 8 values (Σ, Σ² of its 4 segments) over its 64 lanes together:
-      // a permlane32 swap + add leaves 4 registers whose lane halves hold different values, a
-      // permlane16 swap + add 2 whose 16-lane rows do, a row-mirror exchange 1 whose 8-lane
-      // halves do; three DPP steps then finish each 8-lane group: group (row r, half h) = value
-      // 2r + h, i.e. segment r's Σ (h 0) or Σ² (h 1).  (≈20 VALU instead of 8 full reductions.)
-      float a[4] = {g1[0], g2[0], g1[1], g2[1]}, b[4] = {g1[2], g2[2], g1[3], g2[3]};
-      float u[4];
+    for (int blk = 0; blk < 2; ++blk) {
+      if (HH != blk) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a[j]), "+v"(b[j]));
-        u[j] = a[j] + b[j];   // lanes 0-31: value j's partial, 32-63: value j + 4's
-      }
-      float w[2];
+        for (int r = 0; r < 4; ++r) {
+          float m[18], o[16];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float x0 = u[j], x1 = u[j + 2];
-        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x0), "+v"(x1));
-        w[j] = x0 + x1;       // row r: value j + 2r
+          for (int q = 0; q < 18; ++q) m[q] = acc[blk][q][r];
+          w2::half_output<HH>(m, o);
+#pragma unroll
+          for (int f = 0; f < 4; ++f)
+            *reinterpret_cast<float4*>(pl + pbase + f * PW + 4 * r) =
+                make_float4(o[4 * f], o[4 * f + 1], o[4 * f + 2], o[4 * f + 3]);
+        }
       }
-      const int lane = tid & 63;
-      const bool hi = (lane & 8) != 0;
-      const float keep = hi ? w[1] : w[0], send = hi ? w[0] : w[1];
-      float x = keep + dpp_read<0x140>(send);   // row_mirror: lane i <-> 15 - i
-      x += dpp_read<0x141>(x);                  // row_half_mirror
-      x += dpp_read<0x4E>(x);                   // quad_perm [2,3,0,1]
-      x += dpp_read<0xB1>(x);                   // quad_perm [1,0,3,2]
-      const float x2 = __shfl_xor(x, 8, 64);    // lane 16r: Σd of segment r, x2 its Σd²
-      if ((lane & 15) == 0) {
-        const int r = lane >> 4;
-        const int J = (tid >> 6) * NIT + 2 * r;   // the segment's first wave instruction
-        const int c = (J << 6) / PCF, piece = ((J << 6) % PCF) >> 6;
+      __syncthreads();
+      if (HH == blk) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float m[18], o[16];
+#pragma unroll
+          for (int q = 0; q < 18; ++q) m[q] = acc[blk][q][r];
+          w2::half_output<HH>(m, o);
+#pragma unroll
+          for (int f = 0; f < 4; ++f) {
+            float4* d = reinterpret_cast<float4*>(pl + pbase + f * PW + 4 * r);
+            const float4 p = *d;
+            *d = make_float4(o[4 * f] + p.x, o[4 * f + 1] + p.y, o[4 * f + 2] + p.z, o[4 * f + 3] + p.w);
+          }
+        }
+      }
+      __syncthreads();
+      // 16 channels × 1024 floats in 16-B chunks; a wave instruction = 1 KB of one channel:
+      // TXB 8: 8 whole rows of the 32×32 block; TXB 4: one whole 16×16 image plane
+      constexpr int PCF = TXB == 8 ? PH * 8 : NI * 64;   // float4 per channel plane
+      constexpr int NIT = 16 * PCF / NT;                  // wave instructions per wave
+      // TXB 8: wave w takes wave instructions 8w … 8w + 7 (1 KB = 8 rows of one channel each), so
+      // each consecutive pair is one 16-row × 32-pixel segment of one channel: the GroupNorm
+      // statistics below accumulate a pair in registers and reduce the wave's 4 segments together
+      static_assert(TXB != 8 || NIT == 8, "TXB 8: eight wave instructions per wave");
+      // (Σd, Σd²) of d = v − p around a pivot p per segment (a value of the segment: its first wave
+      // instruction's lane-0 x), so a channel whose mean is far from 0 relative to its spread loses
+      // nothing to cancellation; the segment leaves as (mean, M2) for Chan's combine (r05)
+      float g1[4] = {0.f, 0.f, 0.f, 0.f}, g2[4] = {0.f, 0.f, 0.f, 0.f}, piv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < NIT; ++i) {
+        const int idx = TXB == 8 ? (((tid >> 6) * NIT + i) << 6) + (tid & 63) : i * NT + tid;
+        const int c = idx / PCF, q = idx % PCF;
+        const float4 v0 = *reinterpret_cast<const float4*>(plane_of(c) + 4 * q);
         const int k = kb * w2::kNC + 16 * blk + c;
-        const int seg = ((y0 + 8 * piece) >> 4) * (W >> 5) + (x0 >> 5);
-        const float p = r == 0 ? piv[0] : r == 1 ? piv[1] : r == 2 ? piv[2] : piv[3];
-        constexpr float inv_n = 1.0f / 512.0f;   // 16 rows × 32 pixels
-        gnp[((size_t)img * K + k) * (size_t)((H >> 4) * (W >> 5)) + seg] =
-            make_float2(p + x * inv_n, fmaxf(x2 - x * (x * inv_n), 0.0f));
+        const float bv = (EPI & 1) ? bias[k] : 0.0f;
+        size_t o;
+        if (TXB == 8) {
+          const int row = q >> 3, c4 = q & 7;
+          o = (((size_t)img * K + k) * H + y0 + row) * W + x0 + 4 * c4;
+        } else {
+          o = ((size_t)(img + (q >> 6)) * K + k) * 256 + 4 * (q & 63);
+        }
+        float4 v = make_float4(v0.x + bv, v0.y + bv, v0.z + bv, v0.w + bv);
+        if (EPI & 2) {
+          const float4 rv = *reinterpret_cast<const float4*>(res + o);
+          v.x += rv.x;
+          v.y += rv.y;
+          v.z += rv.z;
+          v.w += rv.w;
+        }
+        if (dbg & 128) __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(y + o));
+        else if (!(dbg & 64)) *reinterpret_cast<float4*>(y + o) = v;
+        if (TXB == 8 && gnp) {   // the next GroupNorm's statistics: this lane's share of (Σd, Σd²)
+          if ((i & 1) == 0) piv[i >> 1] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v.x)));
+          const float p = piv[i >> 1];
+          const float dx = v.x - p, dy = v.y - p, dz = v.z - p, dw = v.w - p;
+          g1[i >> 1] += (dx + dy) + (dz + dw);
+          g2[i >> 1] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        }
       }
+      if (TXB == 8 && gnp) {
+        // Reduce the wave's 8 values (Σ, Σ² of its 4 segments) over its 64 lanes together:
+        // a permlane32 swap + add leaves 4 registers whose lane halves hold different values, a
+        // permlane16 swap + add 2 whose 16-lane rows do, a row-mirror exchange 1 whose 8-lane
+        // halves do; three DPP steps then finish each 8-lane group: group (row r, half h) = value
+        // 2r + h, i.e. segment r's Σ (h 0) or Σ² (h 1).  (≈20 VALU instead of 8 full reductions.)
+        float a[4] = {g1[0], g2[0], g1[1], g2[1]}, b[4] = {g1[2], g2[2], g1[3], g2[3]};
+        float u[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a[j]), "+v"(b[j]));
+          u[j] = a[j] + b[j];   // lanes 0-31: value j's partial, 32-63: value j + 4's
+        }
+        float w[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          float x0 = u[j], x1 = u[j + 2];
+          asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x0), "+v"(x1));
+          w[j] = x0 + x1;       // row r: value j + 2r
+        }
+        const int lane = tid & 63;
+        const bool hi = (lane & 8) != 0;
+        const float keep = hi ? w[1] : w[0], send = hi ? w[0] : w[1];
+        float x = keep + dpp_read<0x140>(send);   // row_mirror: lane i <-> 15 - i
+        x += dpp_read<0x141>(x);                  // row_half_mirror
+        x += dpp_read<0x4E>(x);                   // quad_perm [2,3,0,1]
+        x += dpp_read<0xB1>(x);                   // quad_perm [1,0,3,2]
+        const float x2 = __shfl_xor(x, 8, 64);    // lane 16r: Σd of segment r, x2 its Σd²
+        if ((lane & 15) == 0) {
+          const int r = lane >> 4;
+          const int J = (tid >> 6) * NIT + 2 * r;   // the segment's first wave instruction
+          const int c = (J << 6) / PCF, piece = ((J << 6) % PCF) >> 6;
+          const int k = kb * w2::kNC + 16 * blk + c;
+          const int seg = ((y0 + 8 * piece) >> 4) * (W >> 5) + (x0 >> 5);
+          const float p = r == 0 ? piv[0] : r == 1 ? piv[1] : r == 2 ? piv[2] : piv[3];
+          constexpr float inv_n = 1.0f / 512.0f;   // 16 rows × 32 pixels
+          gnp[((size_t)img * K + k) * (size_t)((H >> 4) * (W >> 5)) + seg] =
+              make_float2(p + x * inv_n, fmaxf(x2 - x * (x * inv_n), 0.0f));
+        }
+      }
+      if (blk == 0) __syncthreads();
     }
-    if (blk == 0) __syncthreads();
   }
 }
 
-template <int EPI, int TXB, int NW = 8>
+template <int EPI, int TXB, int NW = 8, bool S2 = false>
 __global__ __launch_bounds__(NW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino2_kernel(
     const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ res, float* __restrict__ y, int nimg, int C, int K, int H, int W, int bw, int bpi,
@@ -1178,7 +1285,8 @@ __global__ __launch_bounds__(NW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)
   __shared__ __attribute__((aligned(16))) float R0[w2::GeoT<TXB, NW>::RAWF], R1[w2::GeoT<TXB, NW>::RAWF],
       R2[(TXB == 4 && NW == 4) ? 4 : w2::GeoT<TXB, NW>::RAWF],
       R3[(TXB == 8 && NW == 8 && SKP_W2_RS4) ? w2::GeoT<TXB, NW>::RAWF : 4];
-  __shared__ __attribute__((aligned(16))) float U0[w2::kUF], U1[w2::kUF], U2[NW == 4 ? 4 : w2::kUF];
+  constexpr int UF = S2 ? w2::kUF2 : w2::kUF;
+  __shared__ __attribute__((aligned(16))) float U0[UF], U1[UF], U2[NW == 4 ? 4 : UF];
   // workgroup → (input-channel split, 32×32-pixel block, channel block); consecutive logical ids
   // share one XCD.  A split sums its csplit input channels into slab sp of y (the workspace).
   const int G = gridDim.x;
@@ -1186,7 +1294,7 @@ __global__ __launch_bounds__(NW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)
   const int Lg = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
   const int sp = Lg / (nblk * nkb);
   const int L = Lg - sp * (nblk * nkb);
-  y += (size_t)sp * nimg * K * ((EPI & 4) ? (H / 2) * (W / 2) : H * W);   // EPI bit 2: stride-2 output
+  y += (size_t)sp * nimg * K * (S2 ? (H / 2) * (W / 2) : H * W);   // S2: stride-2 output
   int tb, kb;
   if (kb_major) {
     kb = L / nblk;
@@ -1210,8 +1318,8 @@ __global__ __launch_bounds__(NW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)
   const W2Smem sm{R0, R1, R2, R3, U0, U1, U2};
   const int c0 = sp * csplit;
   if (wv < NW / 2)
-    wino2_body<EPI, 0, TXB, NW>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
-  else wino2_body<EPI, 1, TXB, NW>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
+    wino2_body<EPI, 0, TXB, NW, false, S2>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
+  else wino2_body<EPI, 1, TXB, NW, false, S2>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
 }
 
 // U2[kb][c][k%32][40]: positions 0..17 at 0..17, 18..35 at 20..37, the rest zero
@@ -1239,6 +1347,27 @@ __global__ void wino2_weights_kernel(const float* __restrict__ w, int K, int C, 
     for (int b = 0; b < 6; ++b) {
       const int p = 6 * a + b;
       out[p < 18 ? p : p + 2] = (float)(t[a][0] * Gm[b][0] + t[a][1] * Gm[b][1] + t[a][2] * Gm[b][2]);
+    }
+}
+
+// The stride-2 form's U = Gs2 g Gs2ᵀ, Gs2 = [1 0 0; 1 0 1; 0 0 1; 0 1 0; 0 1 0], in fp64 → fp32:
+// U[kb][c][k%32][28], positions 0..14 at 0..14, 15..24 at 16..25, the rest zero
+__global__ void wino2s2_weights_kernel(const float* __restrict__ w, int K, int C, float* __restrict__ U) {
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (i >= (long long)K * C) return;
+  const int k = (int)(i / C), c = (int)(i - (long long)k * C);
+  double g[9];
+  for (int u = 0; u < 9; ++u) g[u] = (double)w[((size_t)k * C + c) * 9 + u];
+  const double Gm[5][3] = {{1.0, 0.0, 0.0}, {1.0, 0.0, 1.0}, {0.0, 0.0, 1.0}, {0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}};
+  double t[5][3];
+  for (int a = 0; a < 5; ++a)
+    for (int v = 0; v < 3; ++v) t[a][v] = Gm[a][0] * g[v] + Gm[a][1] * g[3 + v] + Gm[a][2] * g[6 + v];
+  float* out = U + (((size_t)(k / w2::kNC) * C + c) * w2::kNC + (k % w2::kNC)) * w2::kUP2;
+  for (int p = 0; p < w2::kUP2; ++p) out[p] = 0.0f;
+  for (int a = 0; a < 5; ++a)
+    for (int b = 0; b < 5; ++b) {
+      const int p = 5 * a + b;
+      out[p < 15 ? p : p + 1] = (float)(t[a][0] * Gm[b][0] + t[a][1] * Gm[b][1] + t[a][2] * Gm[b][2]);
     }
 }
 
@@ -1352,11 +1481,22 @@ extern "C" int skp_wino2_weights(const float* w, int K, int C, int flip, float* 
   return SKP_OK;
 }
 
+extern "C" int skp_wino2s2_weights(const float* w, int K, int C, float* U, void* stream) {
+  SKP_CHECK_ARG(w && U, "null pointer");
+  SKP_CHECK_ARG(K > 0 && C > 0, "non-positive shape");
+  SKP_CHECK_ARG(K % w2::kNC == 0, "output channels must be a multiple of 32");
+  const long long n = (long long)K * C;
+  hipLaunchKernelGGL(wino2s2_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), w, K,
+                     C, U);
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
 // The VAE's Downsample2D (diffusers: F.pad(x, (0, 1, 0, 1)) then a 3×3 stride-2 convolution; reference
 // ptp_utils.py:289-304 encodes through it): y[oy, ox] taps rows 2oy..2oy+2 and columns 2ox..2ox+2 with a
-// zero row / column past the bottom-right edge, which is exactly the stride-1, pad-1 convolution sampled at
-// the odd positions (2oy + 1, 2ox + 1).  The Winograd kernel computes the 32×32 blocks and its epilogue
-// stores only the odd rows / columns (+ bias): no padded copy, no NCHW↔NHWC transposes, no bias pass.
+// zero row / column past the bottom-right edge.  The S2 form of wino2_body computes it as 2×2 output tiles of
+// 25 products (U from skp_wino2s2_weights) on the stride-1 kernel's staged regions, whose out-of-range row /
+// column is that zero pad, with the bias in its epilogue: no padded copy, no NCHW↔NHWC transposes, no bias pass.
 namespace {
 // flag 128 of the kernels' flag word: non-temporal output stores, for outputs of at least 256 MB
 // (larger than the Infinity Cache: the next layer re-reads them from HBM either way, and the stream
@@ -1367,8 +1507,8 @@ int wino_nt_flag(long long out_bytes, int nsplit) {
 }
 }  // namespace
 
-extern "C" int skp_conv3x3s2_wino2(const float* x, const float* U, const float* bias, float* y, int B, int C, int K,
-                                   int H, int W, int nsplit, float* ws, void* stream) {
+extern "C" int skp_conv3x3s2_f2(const float* x, const float* U, const float* bias, float* y, int B, int C, int K,
+                                int H, int W, int nsplit, float* ws, void* stream) {
   SKP_CHECK_ARG(x && U && y, "null pointer");
   SKP_CHECK_ARG(B > 0 && C > 0 && K > 0 && H > 0 && W > 0, "non-positive shape");
   SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
@@ -1378,7 +1518,6 @@ extern "C" int skp_conv3x3s2_wino2(const float* x, const float* U, const float* 
   SKP_CHECK_ARG(nsplit == 1 || ws, "split-K needs a workspace of nsplit·B·K·(H/2)·(W/2) floats");
   SKP_CHECK_ARG(aligned16(x) && aligned16(U) && aligned16(y) && (!ws || aligned16(ws)), "tensors must be 16-byte aligned");
   SKP_CHECK_ARG((long long)B * C * H * W * 4 < 0x7fffffffLL, "input larger than 2 GiB (32-bit buffer offsets)");
-  // half-height blocks (see skp_conv3x3_wino2)
   const int bw = W / 32, bpi = (H / 16) * bw;
   const long long nblk = (long long)B * bpi;
   const int nkb = K / w2::kNC;
@@ -1388,11 +1527,11 @@ extern "C" int skp_conv3x3s2_wino2(const float* x, const float* U, const float* 
   const dim3 grid((unsigned)(nblk * nkb * nsplit));
   const int fl = SKP_WINO2_DEBUG | wino_nt_flag((long long)B * K * (H / 2) * (W / 2) * 4, nsplit);
   if (nsplit == 1 && bias)
-    hipLaunchKernelGGL((wino2_kernel<5, 8, 4>), grid, dim3(4 * WAVE), 0, st, x, U, bias, nullptr, out, B, C, K, H, W,
-                       bw, bpi, (int)nblk, nkb, 0, C / nsplit, fl, nullptr);
-  else
-    hipLaunchKernelGGL((wino2_kernel<4, 8, 4>), grid, dim3(4 * WAVE), 0, st, x, U, nullptr, nullptr, out, B, C, K, H,
+    hipLaunchKernelGGL((wino2_kernel<1, 8, 4, true>), grid, dim3(4 * WAVE), 0, st, x, U, bias, nullptr, out, B, C, K, H,
                        W, bw, bpi, (int)nblk, nkb, 0, C / nsplit, fl, nullptr);
+  else
+    hipLaunchKernelGGL((wino2_kernel<0, 8, 4, true>), grid, dim3(4 * WAVE), 0, st, x, U, nullptr, nullptr, out, B, C, K,
+                       H, W, bw, bpi, (int)nblk, nkb, 0, C / nsplit, fl, nullptr);
   SKP_LAUNCH_CHECK();
   if (nsplit > 1) return splitk_reduce(ws, nsplit, B, K, (H / 2) * (W / 2), bias, nullptr, y, st);
   return SKP_OK;

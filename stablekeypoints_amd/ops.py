@@ -1617,8 +1617,12 @@ def _wino_u(weight, flip, v2=False):
         return hit[1]
     w = _c(weight.detach())
     K, C = (w.shape[0], w.shape[1]) if not flip else (w.shape[1], w.shape[0])
-    U = torch.empty(K * C * (40 if v2 else 36), device=w.device, dtype=F32)
-    call("skp_wino2_weights" if v2 else "skp_wino_weights", ptr(w), K, C, int(flip), ptr(U), stream(w.device))
+    if v2 == "s2":   # the stride-2 form's 25 positions in rows of 28 (skp_wino2s2_weights; never flipped)
+        U = torch.empty(K * C * 28, device=w.device, dtype=F32)
+        call("skp_wino2s2_weights", ptr(w), K, C, ptr(U), stream(w.device))
+    else:
+        U = torch.empty(K * C * (40 if v2 else 36), device=w.device, dtype=F32)
+        call("skp_wino2_weights" if v2 else "skp_wino_weights", ptr(w), K, C, int(flip), ptr(U), stream(w.device))
     per[(flip, v2)] = (weight._version, U)
     return U
 
@@ -1859,15 +1863,19 @@ def conv1x1(x, weight):
 
 # A/B: 0 = the VAE's stride-2 downsampling convolutions run as F.pad + MIOpen (r02)
 WINO_S2 = True
-WINO_S2_MIN_PIXELS = 384 * 384   # 256² / 128² measured neutral on the copy-free kernel (profiles/r05y_s2_wino_ab.txt)
+WINO_S2_MIN_PIXELS = 128 * 128   # the smallest level measured (profiles/r09a_s2f2_kernels.txt)
 
 
 def conv3x3_s2_eligible(x, weight):
     B, C, H, W = x.shape
     K = weight.shape[0]
-    # measured at batch 8 (tools/conv_s2_time.py): 512² × 128 ch 2.21 vs 2.75 ms for pad + MIOpen; at
-    # 256² × 256 (1.89 vs 1.85) and 128² × 512 (1.81 vs 1.53) MIOpen's implicit GEMM is as fast or
-    # faster than the 4×-redundant Winograd blocks, so only the large-image levels take this path
+    # measured at batch 8 (tools/conv_s2_time.py, three alternating repeats, ms; profiles/r09a_s2f2_kernels.txt):
+    #                   skp_conv3x3s2_f2   sampled F(4×4, 3×3)   edge-pad copy + MIOpen
+    #   512² × 128 ch   1.33-1.34          1.91-1.93             2.47-2.48
+    #   256² × 256 ch   1.24-1.25          1.78-1.80             1.85
+    #   128² × 512 ch   1.20-1.22          1.74-1.75             1.55-1.56
+    # every repeat of the 25-product kernel is below every repeat of both alternatives at all three
+    # VAE levels, so all of them take it (the sampled kernel it replaced is gone from the library)
     return (WINO_S2 and x.is_cuda and x.dtype == F32 and tuple(weight.shape[1:]) == (C, 3, 3) and C % 4 == 0
             and K % 32 == 0 and H % 32 == 0 and W % 32 == 0 and H * W >= WINO_S2_MIN_PIXELS
             and not weight.requires_grad and not (torch.is_grad_enabled() and x.requires_grad))
@@ -1875,10 +1883,10 @@ def conv3x3_s2_eligible(x, weight):
 
 def conv3x3_s2(x, weight, bias=None):
     """diffusers' Downsample2D(padding=0) — F.pad(x, (0, 1, 0, 1)) then a 3×3 / stride-2 conv2d —
-    forward only (the frozen VAE encoder runs without gradient): skp_conv3x3s2_wino2, the stride-1
-    pad-1 Winograd convolution sampled at the odd rows / columns (the same taps, the same zero
-    row / column past the bottom-right edge) with the bias in its epilogue.  (B, C, H, W) →
-    (B, K, H/2, W/2)."""
+    forward only (the frozen VAE encoder runs without gradient): skp_conv3x3s2_f2, the stride-2
+    minimal-product form (2×2 output tiles of 25 products on the stride-1 kernel's staged regions,
+    whose out-of-range row / column is the zero pad past the bottom-right edge) with the bias in
+    its epilogue.  (B, C, H, W) → (B, K, H/2, W/2)."""
     _lib.require_device(x)
     if not conv3x3_s2_eligible(x, weight):
         raise ValueError(f"conv3x3_s2: unsupported x {tuple(x.shape)} / weight {tuple(weight.shape)}")
@@ -1886,15 +1894,15 @@ def conv3x3_s2(x, weight, bias=None):
     B, C, H, W = x.shape
     K = weight.shape[0]
     y = torch.empty(B, K, H // 2, W // 2, device=x.device, dtype=F32)
-    U = _wino_u(weight, False, True)
+    U = _wino_u(weight, False, "s2")
     b = None if bias is None else _c(bias.detach())
     bmax = max(1, (2 ** 31 - 1) // (C * H * W * 4))   # 32-bit buffer offsets into x
     for b0 in range(0, B, bmax):
         b1 = min(B, b0 + bmax)
         _, nsplit, _ = _wino_plan(b1 - b0, C, K, H, W)
         ws = torch.empty(nsplit, b1 - b0, K, H // 2, W // 2, device=x.device, dtype=F32) if nsplit > 1 else None
-        with _timed("skp_conv3x3s2_wino2", 0):
-            call("skp_conv3x3s2_wino2", ptr(x[b0:b1]), ptr(U), ptr(b), ptr(y[b0:b1]), b1 - b0, C, K, H, W, nsplit,
+        with _timed("skp_conv3x3s2_f2", 0):
+            call("skp_conv3x3s2_f2", ptr(x[b0:b1]), ptr(U), ptr(b), ptr(y[b0:b1]), b1 - b0, C, K, H, W, nsplit,
                  ptr(ws), stream(x.device))
     return y
 
