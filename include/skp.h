@@ -485,6 +485,29 @@ int skp_tta_reduce_workspace(int B, int n, int S);
 int skp_tta_reduce(const float* maps, int B, int C, int n, int S, const float* theta_inv, float* pos, float* avg,
                    void* workspace, void* stream);
 
+/* The scored TTA reduce: skp_tta_reduce (eval.py:327-355, then eval.find_max_pixel, eval.py:39-60)
+ * and, in the same passes and without the average in memory, three scores per image and token and
+ * the eval.pixel_from_weighted_avg centroid (eval.py:113-155) around the peak.
+ *   pos, avg: skp_tta_reduce's, bit for bit.  refined (B, n, 2), scores (B, n, 3).  With a the
+ *   average of image b and token t, (r*, c*) its argmax and K the pixels (r, c) with
+ *   sqrt((r − r*)² + (c − c*)²) <= distance in float:
+ *   scores[b,t,0] = a[r*, c*]                                         (the peak)
+ *   scores[b,t,1] = (float)(Σ_K a / (Σ a + 1e-6)), both sums in double   (the concentration)
+ *   scores[b,t,2] = num[r*, c*] / C, num = Σ_c sample(ones, …)          (the coverage)
+ *   refined[b,t]  = (Σ_K r·(a / denom) + 0.5, Σ_K c·(a / denom) + 0.5), denom = (float)Σ_K a + 1e-6f,
+ *                   the products in float, their sums in double: skp_weighted_avg's arithmetic.
+ * Three launches, no atomics: the tile kernel also leaves each tile's Σ a (double from the lane
+ * upward, a fixed tree), the merge sums them in a fixed order, and one workgroup per image and
+ * token recomputes a on the box r* ± ⌊distance⌋, c* ± ⌊distance⌋ (clipped to the plane) with the
+ * tile kernel's arithmetic.  Deterministic.  A token whose maps hold NaN or inf gets unspecified
+ * scores.
+ * workspace: skp_tta_reduce_scored_workspace(B, n, S) bytes (−1 on a bad shape), 8-B aligned.
+ * Rejected before any launch: what skp_tta_reduce rejects, a null refined or scores, and a
+ * distance outside (0, 16].                                                                    */
+int skp_tta_reduce_scored_workspace(int B, int n, int S);
+int skp_tta_reduce_scored(const float* maps, int B, int C, int n, int S, const float* theta_inv, float distance,
+                          float* pos, float* refined, float* scores, float* avg, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

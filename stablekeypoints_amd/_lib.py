@@ -102,6 +102,8 @@ _SIGS = {
                          _c_int, _c_int, _c_int, _c_int, _p, _p],
     "skp_tta_reduce_workspace": [_c_int, _c_int, _c_int],
     "skp_tta_reduce": [_p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p],
+    "skp_tta_reduce_scored_workspace": [_c_int, _c_int, _c_int],
+    "skp_tta_reduce_scored": [_p, _c_int, _c_int, _c_int, _c_int, _p, _c_float, _p, _p, _p, _p, _p, _p],
     "skp_version": [],
 }
 

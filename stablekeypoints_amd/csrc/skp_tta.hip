@@ -14,6 +14,15 @@
 // Two launches, no atomics: the tile kernel (one workgroup per image and 64 x 4-pixel piece of a
 // four-row band) leaves one (value, linear index) partial per token and tile; the merge kernel
 // reduces each (image, token)'s partials (the greater value wins, on equal values the lower index).
+//
+// The scored reduce (skp_tta_reduce_scored) adds, without the average in memory: the tile kernel's
+// scored instantiation leaves the sum of each tile's averaged values beside its partial (double
+// from the lane upward, a fixed tree), the scored merge sums them in a fixed order, and a third
+// launch (one workgroup per image and token) recomputes the average on the box around the peak
+// with the same functions, hence the same bits, for the centroid of eval.py:113-155, the
+// concentration and the coverage.  Three launches, no atomics.
+#include <type_traits>
+
 #include "skp_warp.h"
 
 using namespace skp;
@@ -40,6 +49,38 @@ __device__ __forceinline__ void wave_best(float& v, int& i) {
   for (int o = 32; o > 0; o >>= 1) c = min(c, __shfl_xor(c, o, 64));
   v = m;
   i = c;
+}
+
+// Full-wave double sum in wave_reduce's tree (skp_common.h): the same DPP controls and row swaps on
+// the two halves of the value, so a step costs VALU moves and no LDS crossbar.  Every lane ends
+// with the same bits, and two runs give the same bits.  Needs all 64 lanes active.
+template <int CTRL>
+__device__ __forceinline__ double dpp_read(double v) {
+  const long long q = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)q, CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(q >> 32), CTRL, 0xF, 0xF, false);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
+}
+__device__ __forceinline__ double wave_sum_tree(double v) {
+  v += dpp_read<0xB1>(v);    // quad_perm [1,0,3,2]
+  v += dpp_read<0x4E>(v);    // quad_perm [2,3,0,1]
+  v += dpp_read<0x141>(v);   // row_half_mirror
+  v += dpp_read<0x140>(v);   // row_mirror
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const long long q = __builtin_bit_cast(long long, v);
+    int lo = (int)q, hi = (int)(q >> 32), wlo = lo, whi = hi;
+    if (s == 0) {
+      asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(lo), "+v"(wlo));
+      asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(hi), "+v"(whi));
+    } else {
+      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(wlo));
+      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(hi), "+v"(whi));
+    }
+    v = __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo) +
+        __builtin_bit_cast(double, ((long long)whi << 32) | (unsigned)wlo);
+  }
+  return v;
 }
 
 // A workgroup takes a tile of kTileW x kTileH pixels, one pixel per thread, each wave a 16 x 4
@@ -104,11 +145,18 @@ struct TileArgs {
   int* part_i;
   int C, n, S;
 };
+struct ScoredTileArgs : TileArgs {
+  double* part_m;           // (B, n, tiles): the sum of the tile's averaged values
+};
+template <bool SCORED>
+using TileArgsOf = std::conditional_t<SCORED, ScoredTileArgs, TileArgs>;
 
 // Tokens t0 … t0 + NT − 1 of this thread's pixel: one pass over the copies, the sums in registers.
-template <int NT>
-__device__ __forceinline__ void tile_pass(const TileArgs& A, int t0, int b, int x, int y, bool inside, int p,
-                                          float (*s_v)[kWaves], int (*s_i)[kWaves]) {
+// SCORED: each token's averaged value also goes, as it is produced, into the tile's mass: lane
+// value (0 outside the plane) -> wave tree -> the four waves in order, all in double.
+template <int NT, bool SCORED>
+__device__ __forceinline__ void tile_pass(const TileArgsOf<SCORED>& A, int t0, int b, int x, int y, bool inside, int p,
+                                          float (*s_v)[kWaves], int (*s_i)[kWaves], double (*s_m)[kWaves]) {
   const int S = A.S, SS = S * S;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float bv[NT];
@@ -148,6 +196,10 @@ __device__ __forceinline__ void tile_pass(const TileArgs& A, int t0, int b, int 
   }
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
+    if constexpr (SCORED) {
+      const double m = wave_sum_tree(inside ? (double)bv[j] : 0.0);
+      if (lane == 0) s_m[j][wid] = m;
+    }
     wave_best(bv[j], bi[j]);
     if (lane == 0) {
       s_v[j][wid] = bv[j];
@@ -168,6 +220,12 @@ __device__ __forceinline__ void tile_pass(const TileArgs& A, int t0, int b, int 
     const size_t o = ((size_t)b * A.n + t0 + j) * gridDim.x + blockIdx.x;
     A.part_v[o] = v;
     A.part_i[o] = i;
+    if constexpr (SCORED) {
+      double m = s_m[j][0];
+#pragma unroll
+      for (int k = 1; k < kWaves; ++k) m += s_m[j][k];
+      A.part_m[o] = m;
+    }
   }
   __syncthreads();
 }
@@ -175,9 +233,11 @@ __device__ __forceinline__ void tile_pass(const TileArgs& A, int t0, int b, int 
 // grid (tiles_x · tiles_y, B).  The tokens go in passes of kTok, the rest in passes of 8, 4, 2, 1
 // (compile-time counts: no branch between a pass's loads).  Four waves per SIMD are asked for, not
 // eight: a pass holds 4·kTok loaded values, and one image of 512² is four waves per SIMD anyway.
-__global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgs A) {
+template <bool SCORED>
+__global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgsOf<SCORED> A) {
   __shared__ float s_v[kTok][kWaves];
   __shared__ int s_i[kTok][kWaves];
+  __shared__ double s_m[SCORED ? kTok : 1][kWaves];
   const int b = blockIdx.y, tile = blockIdx.x, S = A.S;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int x = (tile % tiles_x(S)) * kTileW + wid * 16 + (lane & 15);
@@ -185,21 +245,21 @@ __global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgs A)
   const bool inside = x < S && y < S;
   const int p = inside ? y * S + x : 0;
   int t0 = 0;
-  for (; t0 + kTok <= A.n; t0 += kTok) tile_pass<kTok>(A, t0, b, x, y, inside, p, s_v, s_i);
+  for (; t0 + kTok <= A.n; t0 += kTok) tile_pass<kTok, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
   const int rest = A.n - t0;   // < kTok <= 15
   if (rest & 8) {
-    tile_pass<8>(A, t0, b, x, y, inside, p, s_v, s_i);
+    tile_pass<8, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
     t0 += 8;
   }
   if (rest & 4) {
-    tile_pass<4>(A, t0, b, x, y, inside, p, s_v, s_i);
+    tile_pass<4, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
     t0 += 4;
   }
   if (rest & 2) {
-    tile_pass<2>(A, t0, b, x, y, inside, p, s_v, s_i);
+    tile_pass<2, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
     t0 += 2;
   }
-  if (rest & 1) tile_pass<1>(A, t0, b, x, y, inside, p, s_v, s_i);
+  if (rest & 1) tile_pass<1, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
 }
 
 // One wave per (image, token): the best of its `parts` partials -> pos (row + 0.5, col + 0.5).
@@ -217,6 +277,124 @@ __global__ __launch_bounds__(WAVE) void tta_merge_kernel(const float* __restrict
   if (threadIdx.x == 0) {
     pos[2 * (size_t)blockIdx.x] = (float)(i / S) + 0.5f;
     pos[2 * (size_t)blockIdx.x + 1] = (float)(i % S) + 0.5f;
+  }
+}
+
+// The scored merge: the same reduction of the (value, index) partials, and the mass partials summed
+// in a fixed order (lane k takes partials k, k + 64, … in order, then the wave tree).  Leaves the
+// peak value, its linear index and the total mass for the window kernel.
+__global__ __launch_bounds__(WAVE) void tta_merge_scored_kernel(const float* __restrict__ part_v,
+                                                                const int* __restrict__ part_i,
+                                                                const double* __restrict__ part_m, int parts, int S,
+                                                                float* __restrict__ pos, float* __restrict__ scores,
+                                                                int* __restrict__ peak_i, double* __restrict__ total) {
+  const size_t o = (size_t)blockIdx.x * parts;
+  float v = -INFINITY;
+  int i = kNoIndex;
+  double m = 0.0;
+  for (int k = threadIdx.x; k < parts; k += WAVE) {
+    if (better(part_v[o + k], part_i[o + k], v, i)) {
+      v = part_v[o + k];
+      i = part_i[o + k];
+    }
+    m += part_m[o + k];
+  }
+  wave_best(v, i);
+  m = wave_sum_tree(m);
+  if (threadIdx.x == 0) {
+    pos[2 * (size_t)blockIdx.x] = (float)(i / S) + 0.5f;
+    pos[2 * (size_t)blockIdx.x + 1] = (float)(i % S) + 0.5f;
+    scores[3 * (size_t)blockIdx.x] = v;
+    peak_i[blockIdx.x] = i;
+    total[blockIdx.x] = m;
+  }
+}
+
+// The TTA average of one pixel of one token, as the tile kernel forms it: the same functions in
+// the same order, so the same bits.  `num` is the pixel's sum of the warped ones.
+__device__ __forceinline__ float average_at(const float* __restrict__ maps, const float* __restrict__ th, int C,
+                                            size_t copy_stride, int y, int x, int S, float& num) {
+#pragma clang fp contract(off)
+  constexpr int kAhead = 4;   // copies whose loads are in flight together; the sums stay in copy order
+  float sum = 0.0f;
+  num = 0.0f;
+  for (int c0 = 0; c0 < C; c0 += kAhead) {
+    Taps t[kAhead];
+    Pair raw[kAhead][2];
+    float ones[kAhead];
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k) {
+      const int c = min(c0 + k, C - 1);   // past the last copy: the last one again, loaded and not added
+      const Bilin g = grid_point(th + 6 * c, y, x, S, S);
+      ones[k] = sample_ones(g, S, S);
+      t[k] = taps_of(g, S);
+      const float* plane = maps + c * copy_stride;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) raw[k][r] = *reinterpret_cast<const Pair*>(plane + t[k].off[r]);
+    }
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k)
+      if (c0 + k < C) {
+        num = __fadd_rn(num, ones[k]);
+        sum = __fadd_rn(sum, sample_taps(raw[k], t[k]));
+      }
+  }
+  const float a = __fdiv_rn(sum, num);
+  return a != a ? 0.0f : a;
+}
+
+// One workgroup per (image, token): the box of rows r* ± ⌊distance⌋ and columns c* ± ⌊distance⌋
+// around the merged peak, clipped to the plane; the average recomputed on it; of the pixels within
+// `distance` of the peak (weighted_avg_kernel's predicate and arithmetic, skp_select.hip) the mass,
+// the centroid, and the mass over the total; the share of the copies that saw the peak pixel.
+constexpr int kMaxDistance = 16;
+constexpr int kMaxBox = (2 * kMaxDistance + 1) * (2 * kMaxDistance + 1);
+__global__ __launch_bounds__(kThreads) void tta_window_kernel(const float* __restrict__ maps,
+                                                              const float* __restrict__ theta_inv, int C, int n, int S,
+                                                              float distance, const int* __restrict__ peak_i,
+                                                              const double* __restrict__ total,
+                                                              float* __restrict__ refined, float* __restrict__ scores) {
+  __shared__ float s_val[kMaxBox];
+  __shared__ double sd[kWaves];
+  __shared__ float s_num;
+  const int SS = S * S, b = blockIdx.x / n, tok = blockIdx.x % n;
+  int peak = peak_i[blockIdx.x];
+  peak = (unsigned)peak < (unsigned)SS ? peak : 0;   // every tile holds a pixel, so it is; the loads below rely on it
+  const int r0 = peak / S, c0 = peak % S, R = (int)distance;
+  const int ylo = max(r0 - R, 0), yhi = min(r0 + R, S - 1), xlo = max(c0 - R, 0), xhi = min(c0 + R, S - 1);
+  const int bw = xhi - xlo + 1, cnt = bw * (yhi - ylo + 1);   // <= kMaxBox: distance <= kMaxDistance
+  const float* th = theta_inv + (size_t)b * C * 6;
+  const float* plane0 = maps + ((size_t)b * C * n + tok) * SS;
+  const float r = (float)r0, c = (float)c0;
+  double tot = 0.0;
+  for (int e = threadIdx.x; e < cnt; e += kThreads) {
+    const int y = ylo + e / bw, x = xlo + e % bw;
+    const float dx = (float)y - r, dy = (float)x - c;
+    float v = 0.0f;
+    if (sqrt_rn(dx * dx + dy * dy) <= distance) {
+      float num;
+      v = average_at(plane0, th, C, (size_t)n * SS, y, x, S, num);
+      if (y == r0 && x == c0) s_num = num;
+    }
+    s_val[e] = v;
+    tot += (double)v;
+  }
+  tot = block_sum(tot, sd);
+  const float denom = (float)tot + 1e-6f;
+  double xs = 0.0, ys = 0.0;
+  for (int e = threadIdx.x; e < cnt; e += kThreads) {
+    const float y = (float)(ylo + e / bw), x = (float)(xlo + e % bw);
+    const float nv = s_val[e] / denom;
+    xs += (double)(y * nv);
+    ys += (double)(x * nv);
+  }
+  xs = block_sum(xs, sd);
+  ys = block_sum(ys, sd);
+  if (threadIdx.x == 0) {
+    refined[2 * (size_t)blockIdx.x] = (float)xs + 0.5f;
+    refined[2 * (size_t)blockIdx.x + 1] = (float)ys + 0.5f;
+    scores[3 * (size_t)blockIdx.x + 1] = (float)(tot / (total[blockIdx.x] + 1e-6));
+    scores[3 * (size_t)blockIdx.x + 2] = __fdiv_rn(s_num, (float)C);
   }
 }
 
@@ -244,9 +422,50 @@ extern "C" int skp_tta_reduce(const float* maps, int B, int C, int n, int S, con
   TileArgs A;
   A.maps = maps, A.theta_inv = theta_inv, A.avg = avg, A.part_v = part_v, A.part_i = part_i;
   A.C = C, A.n = n, A.S = S;
-  hipLaunchKernelGGL(tta_tile_kernel, dim3(tiles, B), dim3(kThreads), 0, st, A);
+  hipLaunchKernelGGL(tta_tile_kernel<false>, dim3(tiles, B), dim3(kThreads), 0, st, A);
   SKP_LAUNCH_CHECK();
   hipLaunchKernelGGL(tta_merge_kernel, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, tiles, S, pos);
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
+// Per image and token: the (value, index) partials, then the mass partials, one of each per tile,
+// then the merged total (double) and peak index (int, padded to 8 bytes).
+extern "C" int skp_tta_reduce_scored_workspace(int B, int n, int S) {
+  if (B <= 0 || n <= 0 || S < 2) return -1;
+  const long long bytes = (long long)B * n * ((long long)tiles_x(S) * tiles_y(S) * 16 + 16);
+  return bytes < (1ll << 31) ? (int)bytes : -1;
+}
+
+extern "C" int skp_tta_reduce_scored(const float* maps, int B, int C, int n, int S, const float* theta_inv,
+                                     float distance, float* pos, float* refined, float* scores, float* avg,
+                                     void* workspace, void* stream) {
+  SKP_CHECK_ARG(maps && theta_inv && pos && refined && scores && workspace, "null pointer");
+  SKP_CHECK_ARG(B > 0 && C > 0 && n > 0 && S > 0, "non-positive shape");
+  SKP_CHECK_ARG(S >= 2, "S must be at least 2 (the two taps of a row are loaded as a pair)");
+  SKP_CHECK_ARG(S < 46341 && (long long)B * C * n * S * S < (1ll << 31), "maps of 2^31 elements or more");
+  SKP_CHECK_ARG(B <= 65535, "more than 65535 images");
+  SKP_CHECK_ARG(skp_tta_reduce_scored_workspace(B, n, S) > 0, "workspace of 2^31 bytes or more");
+  SKP_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
+  SKP_CHECK_ARG(distance > 0.0f && distance <= (float)kMaxDistance, "distance must be in (0, 16]");
+  const int tiles = tiles_x(S) * tiles_y(S);
+  const size_t parts = (size_t)B * n * tiles;
+  float* part_v = static_cast<float*>(workspace);
+  int* part_i = reinterpret_cast<int*>(part_v + parts);
+  double* part_m = reinterpret_cast<double*>(part_i + parts);
+  double* total = part_m + parts;
+  int* peak_i = reinterpret_cast<int*>(total + (size_t)B * n);
+  hipStream_t st = as_stream(stream);
+  ScoredTileArgs A;
+  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg, A.part_v = part_v, A.part_i = part_i, A.part_m = part_m;
+  A.C = C, A.n = n, A.S = S;
+  hipLaunchKernelGGL(tta_tile_kernel<true>, dim3(tiles, B), dim3(kThreads), 0, st, A);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tta_merge_scored_kernel, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, part_m, tiles, S, pos,
+                     scores, peak_i, total);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tta_window_kernel, dim3(B * n), dim3(kThreads), 0, st, maps, theta_inv, C, n, S, distance, peak_i,
+                     total, refined, scores);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }

@@ -10,6 +10,7 @@ keypoints from it and scores them with the reference's five metrics (``keypoint_
 captures and the whole TTA reduce (inverse warps, sums, ratio, argmax) in one kernel,
 ``skp_tta_reduce``.
 """
+import collections
 import contextlib
 import os
 
@@ -224,11 +225,14 @@ def evaluate(ldm, context, indices, regressor, device="cuda", from_where=("down_
     return mean
 
 
+KeypointScores = collections.namedtuple("KeypointScores", ["peak", "concentration", "coverage", "refined"])
+
+
 @torch.no_grad()
 def predict_keypoints(ldm, images, context, indices, regressor=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
                       noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
                       augmentation_iterations=20, max_loc_strategy="argmax", controllers=None, upscale_size=512,
-                      image_batch=None, return_maps=False):
+                      image_batch=None, return_maps=False, return_scores=False, score_distance=5):
     """Keypoints of a batch of unlabelled images (extra: the use the reference's demo ends in,
     ``visualize_keypoints``: TTA maps → ``find_max_pixel(map) / 512``, which draws the points and
     does not return them).
@@ -246,7 +250,13 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
     ``max_loc_strategy="weighted_avg"`` ``pixel_from_weighted_avg`` of the averages.  With a
     ``regressor`` (2n, 2K) also ``((p.reshape(B, -1) − 0.5) @ W + 0.5).reshape(B, -1, 2)``; with
     ``return_maps`` also the (B, n, S, S) averages.  More than one output comes as a tuple in that
-    order.  Single process only: under a process group of more than one rank it raises.
+    order.  With ``return_scores`` each pass is reduced by ``ops.tta_reduce_scored`` and a
+    ``KeypointScores(peak, concentration, coverage, refined)`` comes last: per image and token the
+    average's peak value, its mass within ``score_distance`` pixels of the peak over its whole mass,
+    the share of the copies that saw the peak pixel (each (B, n)), and the
+    ``pixel_from_weighted_avg`` centroid around the peak / ``upscale_size`` (B, n, 2); the other
+    outputs are what they are without it.  Single process only: under a process group of more
+    than one rank it raises.
     """
     from .optimize import _world
     if _world()[0] > 1:
@@ -270,7 +280,7 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
     per_pass = max(1, int(image_batch))
     weighted = max_loc_strategy == "weighted_avg"
     want_avg = weighted or return_maps
-    pos, avgs = [], []
+    pos, avgs, refs, scos = [], [], [], []
     for i0 in range(0, B, per_pass):
         nb = min(per_pass, B - i0)
         aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
@@ -281,8 +291,14 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
         maps = torch.stack([per[k][b] for b in range(nb * C) for k in range(len(per))])
         if tuple(maps.shape) != (nb * C, n, S, S):
             raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
-        p, avg = ops.tta_reduce(maps.reshape(nb, C, n, S, S), T.theta_inverse().reshape(nb, C, 2, 3).to(device),
-                                return_avg=want_avg)
+        th_inv = T.theta_inverse().reshape(nb, C, 2, 3).to(device)
+        if return_scores:
+            p, ref, sco, avg = ops.tta_reduce_scored(maps.reshape(nb, C, n, S, S), th_inv, distance=score_distance,
+                                                     return_avg=want_avg)
+            refs.append(ref)
+            scos.append(sco)
+        else:
+            p, avg = ops.tta_reduce(maps.reshape(nb, C, n, S, S), th_inv, return_avg=want_avg)
         del maps, per
         if weighted:   # pixel_from_weighted_avg zeroes its input in place: the returned maps stay whole
             p = pixel_from_weighted_avg(avg.clone().reshape(nb * n, S, S) if return_maps else
@@ -297,4 +313,7 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
         out.append(((kp.reshape(B, -1) - 0.5) @ W + 0.5).reshape(B, -1, 2))
     if return_maps:
         out.append(torch.cat(avgs))
+    if return_scores:
+        sco = torch.cat(scos)
+        out.append(KeypointScores(sco[..., 0], sco[..., 1], sco[..., 2], torch.cat(refs) / S))
     return out[0] if len(out) == 1 else tuple(out)

@@ -71,6 +71,10 @@ def build_parser():
     p.add_argument("--num_gpus", type=int, default=-1,
                    help="ranks to start, one per GPU (-1 = every visible GPU, as the reference's DataParallel "
                         "over torch.cuda.device_count(), optimize_token.py:42-50); ignored under a launcher")
+    p.add_argument("--keypoint_scores", action="store_true",
+                   help="predict stage only: also write keypoint_scores.pt (M, n, 3) = peak, concentration and "
+                        "coverage per keypoint, refined_keypoints.pt (M, n, 2), the sub-pixel centroid around each "
+                        "peak, and keypoint_scores.csv")
     return p
 
 
@@ -105,7 +109,10 @@ def predict_stage(args, ldm, controllers, batch=4):
     ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
     the saved ``embedding.pt`` and ``indices.pt``.  Writes ``keypoints.pt`` (M, n, 2) = (row, col) / 512,
     ``regressed_keypoints.pt`` when ``regressor.pt`` is there, and ``keypoints.csv`` (one row per image and no
-    header: index, file name where the reader has one, the n (row, col) pairs, then the regressed pairs)."""
+    header: index, file name where the reader has one, the n (row, col) pairs, then the regressed pairs).
+    With ``--keypoint_scores`` also ``keypoint_scores.pt`` (M, n, 3) = (peak, concentration, coverage),
+    ``refined_keypoints.pt`` (M, n, 2) and ``keypoint_scores.csv`` (no header: index, file name where the
+    reader has one, then per token refined row, refined col, peak, concentration, coverage)."""
     import csv
     from .datasets import make_dataset
     from .eval import predict_keypoints
@@ -116,7 +123,7 @@ def predict_stage(args, ldm, controllers, batch=4):
     dataset = make_dataset(args.dataset_name, args.dataset_loc, max_len=args.max_len, validation=args.validation,
                            split="test")
     names = _image_names(dataset)
-    kps, regs = [], []
+    kps, regs, scos, refs = [], [], [], []
     for i0 in range(0, len(dataset), batch):
         images = torch.stack([dataset[i]["img"] for i in range(i0, min(i0 + batch, len(dataset)))])
         out = predict_keypoints(ldm, images, embedding, indices.cpu(), regressor=regressor, device=args.device,
@@ -124,7 +131,13 @@ def predict_stage(args, ldm, controllers, batch=4):
                                 augment_degrees=args.augment_degrees, augment_scale=args.augment_scale,
                                 augment_translate=args.augment_translate,
                                 augmentation_iterations=args.augmentation_iterations,
-                                max_loc_strategy=args.max_loc_strategy, controllers=controllers)
+                                max_loc_strategy=args.max_loc_strategy, controllers=controllers,
+                                return_scores=args.keypoint_scores)
+        if args.keypoint_scores:
+            sc = out[-1]
+            out = out[0] if len(out) == 2 else out[:-1]
+            scos.append(torch.stack([sc.peak, sc.concentration, sc.coverage], dim=-1).cpu())
+            refs.append(sc.refined.cpu())
         kp, reg = out if regressor is not None else (out, None)
         kps.append(kp.cpu())
         if reg is not None:
@@ -143,6 +156,17 @@ def predict_stage(args, ldm, controllers, batch=4):
             if regressor is not None:
                 row += [repr(float(v)) for v in regs[i].reshape(-1)]
             w.writerow(row)
+    if args.keypoint_scores:
+        scos = torch.cat(scos) if scos else torch.zeros(0, n, 3)
+        refs = torch.cat(refs) if refs else torch.zeros(0, n, 2)
+        torch.save(scos, os.path.join(folder, "keypoint_scores.pt"))
+        torch.save(refs, os.path.join(folder, "refined_keypoints.pt"))
+        with open(os.path.join(folder, "keypoint_scores.csv"), "w", newline="") as fh:
+            w = csv.writer(fh)
+            for i in range(scos.shape[0]):
+                row = [i] + ([names[i]] if names is not None else [])
+                row += [repr(float(v)) for v in torch.cat([refs[i], scos[i]], dim=-1).reshape(-1)]
+                w.writerow(row)
     print(f"predict: {kps.shape[0]} images, {n} keypoints each -> {os.path.join(folder, 'keypoints.pt')}", flush=True)
 
 

@@ -2168,3 +2168,52 @@ def tta_reduce(maps, theta_inv, return_avg=False):
     with _timed("skp_tta_reduce", tta_reduce_bytes(B, C, n, S, return_avg)):
         call("skp_tta_reduce", ptr(maps), B, C, n, S, ptr(th), ptr(pos), ptr(avg), ptr(ws), stream(dev))
     return pos, avg
+
+
+_TTA_SCORED_WS = {}   # (device, B, n, S) -> workspace of skp_tta_reduce_scored_workspace bytes
+
+
+def tta_reduce_scored_bytes(B, C, n, S, distance=5, avg=False):
+    """Byte model of skp_tta_reduce_scored: ``tta_reduce_bytes`` plus the window kernel's re-reads,
+    two 8-byte pairs per copy for each of the at most (2⌊distance⌋ + 1)² pixels around a peak."""
+    side = 2 * int(distance) + 1
+    return tta_reduce_bytes(B, C, n, S, avg) + 16 * B * n * C * side * side
+
+
+def tta_reduce_scored(maps, theta_inv, distance=5, return_avg=False):
+    """``tta_reduce`` with confidence scores and a sub-pixel position (skp_tta_reduce_scored).
+
+    Returns ``(pos, refined, scores, avg)``: ``pos`` and ``avg`` are ``tta_reduce``'s, bit for bit;
+    ``refined`` (B, n, 2) is the ``pixel_from_weighted_avg`` centroid of the average's pixels
+    within ``distance`` of its peak; ``scores`` (B, n, 3) holds per token the peak value
+    (``[..., 0]``), the concentration (``[..., 1]``: the average's mass within ``distance`` of
+    the peak over its whole mass) and the coverage (``[..., 2]``: the share of the C copies that
+    saw the peak pixel).  The average is not written unless ``return_avg``.  ``0 < distance <= 16``.
+    """
+    _lib.require_device(maps, theta_inv)
+    if maps.dim() != 5 or maps.shape[-1] != maps.shape[-2]:
+        raise ValueError(f"tta_reduce_scored: maps must be (B, C, n, S, S), got {tuple(maps.shape)}")
+    maps = _c(maps)
+    B, C, n, S, _ = maps.shape
+    if tuple(theta_inv.shape) != (B, C, 2, 3):
+        raise ValueError(f"tta_reduce_scored: theta_inv must be ({B}, {C}, 2, 3), got {tuple(theta_inv.shape)}")
+    distance = float(distance)
+    if not 0.0 < distance <= 16.0:
+        raise ValueError(f"tta_reduce_scored: distance must be in (0, 16], got {distance}")
+    dev = maps.device
+    th = _c(theta_inv.to(dev))
+    key = (dev, B, n, S)
+    ws = _TTA_SCORED_WS.get(key)
+    if ws is None:
+        nbytes = _lib.lib().skp_tta_reduce_scored_workspace(B, n, S)
+        if nbytes <= 0:
+            raise ValueError(f"tta_reduce_scored: bad shape B={B}, n={n}, S={S}")
+        ws = _TTA_SCORED_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
+    refined = torch.empty(B, n, 2, device=dev, dtype=F32)
+    scores = torch.empty(B, n, 3, device=dev, dtype=F32)
+    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
+    with _timed("skp_tta_reduce_scored", tta_reduce_scored_bytes(B, C, n, S, distance, return_avg)):
+        call("skp_tta_reduce_scored", ptr(maps), B, C, n, S, ptr(th), distance, ptr(pos), ptr(refined), ptr(scores),
+             ptr(avg), ptr(ws), stream(dev))
+    return pos, refined, scores, avg
