@@ -35,6 +35,8 @@
 // The backward of the same convolution w.r.t. its input is the same correlation of dy with
 // the 180°-rotated, in/out-transposed kernel: skp_wino_weights(flip=1) builds that U.
 #include <cstdlib>
+#include <initializer_list>
+#include <type_traits>
 
 #include "skp_common.h"
 #include "skp_gn.h"   // gn_coef, gn_elem: the GroupNorm(+SiLU) fused into the transform pass
@@ -340,7 +342,18 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
   }
 }
 
-// U[kb][c][k%32][36] = G g Gᵀ in fp64, g = w[k][c] (flip 0) or rot180(w[c][k]) (flip 1)
+// G of F(4×4, 3×3) at the points (0, 1, −1, 1/2, −2, ∞)
+__device__ constexpr double kG[6][3] = {{1.0, 0.0, 0.0},
+                                        {1.0 / 3, 1.0 / 3, 1.0 / 3},
+                                        {-1.0 / 3, 1.0 / 3, -1.0 / 3},
+                                        {-16.0 / 15, -8.0 / 15, -4.0 / 15},
+                                        {1.0 / 15, -2.0 / 15, 4.0 / 15},
+                                        {0.0, 0.0, 1.0}};
+
+// U[kb][c][k%32][ROW] = G g Gᵀ in fp64, g = w[k][c] (flip 0) or rot180(w[c][k]) (flip 1).
+// ROW 36 (wino_f4_kernel): the 36 positions; ROW 40 (wino2_kernel): positions 0..17 at 0..17,
+// 18..35 at 20..37, the rest zero.
+template <int ROW>
 __global__ void wino_weights_kernel(const float* __restrict__ w, int K, int C, int flip, float* __restrict__ U) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (i >= (long long)K * C) return;
@@ -350,31 +363,90 @@ __global__ void wino_weights_kernel(const float* __restrict__ w, int K, int C, i
     for (int v = 0; v < 3; ++v)
       g[3 * u + v] = flip ? (double)w[((size_t)c * K + k) * 9 + (2 - u) * 3 + (2 - v)]
                           : (double)w[((size_t)k * C + c) * 9 + u * 3 + v];
-  const double Gm[6][3] = {{1.0, 0.0, 0.0},
-                           {1.0 / 3, 1.0 / 3, 1.0 / 3},
-                           {-1.0 / 3, 1.0 / 3, -1.0 / 3},
-                           {-16.0 / 15, -8.0 / 15, -4.0 / 15},
-                           {1.0 / 15, -2.0 / 15, 4.0 / 15},
-                           {0.0, 0.0, 1.0}};
   double t[6][3];
   for (int a = 0; a < 6; ++a)
-    for (int v = 0; v < 3; ++v) t[a][v] = Gm[a][0] * g[v] + Gm[a][1] * g[3 + v] + Gm[a][2] * g[6 + v];
-  float* out = U + (((size_t)(k / kNC) * C + c) * kNC + (k % kNC)) * kP;
+    for (int v = 0; v < 3; ++v) t[a][v] = kG[a][0] * g[v] + kG[a][1] * g[3 + v] + kG[a][2] * g[6 + v];
+  float* out = U + (((size_t)(k / kNC) * C + c) * kNC + (k % kNC)) * ROW;
+  if (ROW != kP)
+    for (int p = 0; p < ROW; ++p) out[p] = 0.0f;
   for (int a = 0; a < 6; ++a)
-    for (int b = 0; b < 6; ++b) out[6 * a + b] = (float)(t[a][0] * Gm[b][0] + t[a][1] * Gm[b][1] + t[a][2] * Gm[b][2]);
+    for (int b = 0; b < 6; ++b) {
+      const int p = 6 * a + b;
+      out[(ROW == kP || p < 18) ? p : p + 2] = (float)(t[a][0] * kG[b][0] + t[a][1] * kG[b][1] + t[a][2] * kG[b][2]);
+    }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool all_aligned16(std::initializer_list<const void*> ps) {   // absent (null) optional tensors pass
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+  return true;
+}
+
+// ---------------------------------------------------------------- argument checks
+// The entry points check their arguments through these and report the first failing check with
+// one SKP_CHECK_ARG (which prefixes the entry's name); nullptr = every check passed.
+const char* weights_args_error(const float* w, const float* U, int K, int C) {
+  if (!(w && U)) return "null pointer";
+  if (!(K > 0 && C > 0)) return "non-positive shape";
+  if (K % kNC != 0) return "output channels must be a multiple of 32";
+  return nullptr;
+}
+
+// What the convolution and vtransform entries differ in:
+enum : unsigned {
+  kHW32 = 1,       // H and W multiples of 32 (otherwise of 4) ...
+  kOr16x16 = 2,    // ... or 16×16 images with B a multiple of 4
+  kStride2 = 4,    // the output (and the split-K workspace) is (H/2, W/2)
+  kOffsets32 = 8,  // x is addressed through 32-bit buffer offsets: at most 2 GiB
+};
+struct ConvArgs {
+  bool ptrs, aligned;            // every required tensor is there; every tensor given is 16-byte aligned
+  const void *ws, *gn_part;      // optional: split-K workspace, GroupNorm partials of the output
+  int B, C, K, H, W, nsplit, G;  // an entry without K, nsplit or G passes 32, 1, 1
+};
+const char* conv_args_error(unsigned form, const ConvArgs& a) {
+  const bool hw32 = a.H % 32 == 0 && a.W % 32 == 0;
+  if (!a.ptrs) return "null pointer";
+  if (a.gn_part) {
+    const bool ok = a.nsplit == 1 && (reinterpret_cast<uintptr_t>(a.gn_part) & 7) == 0;
+    if (form & kOr16x16) {
+      if (!(ok && hw32)) return "gn_part: one split, H and W multiples of 32, 8-byte aligned";
+    } else if (!ok) {
+      return "gn_part: one split, 8-byte aligned";
+    }
+  }
+  if (!(a.B > 0 && a.C > 0 && a.K > 0 && a.H > 0 && a.W > 0)) return "non-positive shape";
+  if (a.C % kCK != 0) return "input channels must be a multiple of 4";
+  if (!(a.G > 0 && a.C % a.G == 0)) return "C must be divisible by G";
+  if (a.K % kNC != 0) return "output channels must be a multiple of 32";
+  if (form & kOr16x16) {
+    if (!(hw32 || (a.H == 16 && a.W == 16 && a.B % 4 == 0)))
+      return "H and W must be multiples of 32, or 16×16 with B a multiple of 4";
+  } else if (form & kHW32) {
+    if (!hw32) return "H and W must be multiples of 32";
+  } else if (!(a.H % 4 == 0 && a.W % 4 == 0)) {
+    return "H and W must be multiples of 4";
+  }
+  if (!(a.nsplit >= 1 && a.C % (kCK * a.nsplit) == 0)) return "nsplit must divide C into multiples of 4";
+  if (!(a.nsplit == 1 || a.ws))
+    return (form & kStride2) ? "split-K needs a workspace of nsplit·B·K·(H/2)·(W/2) floats"
+                             : "split-K needs a workspace of nsplit·B·K·H·W floats";
+  if (!a.aligned) return "tensors must be 16-byte aligned";
+  if (!(form & kHW32) && (long long)a.B * (a.H / 4) * (a.W / 4) > 0x7fffffffLL - kMT) return "too many tiles";
+  if ((form & kOffsets32) && !((long long)a.B * a.C * a.H * a.W * 4 < 0x7fffffffLL))
+    return "input larger than 2 GiB (32-bit buffer offsets)";
+  return nullptr;
+}
+constexpr long long kMaxGrid = 0x7fffffffLL;
 
 }  // namespace
 
 extern "C" int skp_wino_weights(const float* w, int K, int C, int flip, float* U, void* stream) {
-  SKP_CHECK_ARG(w && U, "null pointer");
-  SKP_CHECK_ARG(K > 0 && C > 0, "non-positive shape");
-  SKP_CHECK_ARG(K % kNC == 0, "output channels must be a multiple of 32");
+  const char* err = weights_args_error(w, U, K, C);
+  SKP_CHECK_ARG(!err, err);
   const long long n = (long long)K * C;
-  hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), w, K, C,
-                     flip, U);
+  hipLaunchKernelGGL(wino_weights_kernel<kP>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), w, K,
+                     C, flip, U);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }
@@ -422,119 +494,129 @@ int splitk_reduce(const float* ws, int nsplit, int B, int K, int HW, const float
   return SKP_OK;
 }
 
+// flag 128 of the region-staged kernels' flag word: non-temporal output stores, for outputs of at
+// least 256 MB (larger than the Infinity Cache: the next layer re-reads them from HBM either way, and
+// the stream then does not evict the input regions / weights the other workgroups re-read from L2)
+int wino_nt_flag(long long out_bytes, int nsplit) {
+  if (nsplit > 1) return 0;   // split-K partials are re-read by the reduction
+  return out_bytes >= (256LL << 20) ? 128 : 0;
+}
+
+// f(std::integral_constant<int, epi>), instantiated for the NEPI epilogues 0..NEPI−1 the entry can ask for
+template <int NEPI, class F>
+auto with_epi(int epi, F&& f) {
+  static_assert(NEPI == 2 || NEPI == 4, "bias only, or bias and residual");
+  if constexpr (NEPI == 4) {
+    if (epi == 2) return f(std::integral_constant<int, 2>{});
+    if (epi == 3) return f(std::integral_constant<int, 3>{});
+  }
+  return epi == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+}
+
+// What every convolution entry does around its launch: one split writes y with bias and residual in
+// the kernel's epilogue (EPI bit 0 / 1); split-K writes its partial sums to the workspace's slabs
+// with a plain epilogue and splitk_reduce adds bias and residual.  launch(epi, out, flags) starts the
+// kernel; hw = pixels per output plane; nt = the kernel knows the non-temporal store flag.
+template <class Launch>
+int conv_launch(const char* entry, const float* bias, const float* residual, float* y, float* ws, int nsplit, int B, int K,
+                int hw, int dbg, bool nt, hipStream_t st, Launch&& launch) {
+  const int epi = nsplit > 1 ? 0 : (bias ? 1 : 0) | (residual ? 2 : 0);
+  launch(epi, nsplit > 1 ? ws : y, dbg | (nt ? wino_nt_flag((long long)B * K * hw * 4, nsplit) : 0));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error(std::string(entry) + ": launch failed: " + hipGetErrorString(e));
+    return SKP_ELAUNCH;
+  }
+  if (nsplit > 1) return splitk_reduce(ws, nsplit, B, K, hw, bias, residual, y, st);
+  return SKP_OK;
+}
+
 }  // namespace
 
 extern "C" int skp_conv3x3_wino(const float* x, const float* U, const float* bias, const float* residual, float* y,
                                 int B, int C, int K, int H, int W, int nsplit, float* ws, void* stream) {
-  SKP_CHECK_ARG(x && U && y, "null pointer");
-  SKP_CHECK_ARG(B > 0 && C > 0 && K > 0 && H > 0 && W > 0, "non-positive shape");
-  SKP_CHECK_ARG(C % kCK == 0, "input channels must be a multiple of 4");
-  SKP_CHECK_ARG(K % kNC == 0, "output channels must be a multiple of 32");
-  SKP_CHECK_ARG(H % 4 == 0 && W % 4 == 0, "H and W must be multiples of 4");
-  SKP_CHECK_ARG(nsplit >= 1 && C % (kCK * nsplit) == 0, "nsplit must divide C into multiples of 4");
-  SKP_CHECK_ARG(nsplit == 1 || ws, "split-K needs a workspace of nsplit·B·K·H·W floats");
-  SKP_CHECK_ARG(aligned16(x) && aligned16(U) && aligned16(y) && (!residual || aligned16(residual)) &&
-                    (!ws || aligned16(ws)),
-                "tensors must be 16-byte aligned");
+  const ConvArgs a{x && U && y, all_aligned16({x, U, y, residual, ws}), ws, nullptr, B, C, K, H, W, nsplit, 1};
+  const char* err = conv_args_error(kOffsets32, a);
   const int tw = W / 4, tpi = (H / 4) * tw;
   const long long ntiles = (long long)B * tpi;
-  SKP_CHECK_ARG(ntiles <= 0x7fffffffLL - kMT, "too many tiles");
-  SKP_CHECK_ARG((long long)B * C * H * W * 4 < 0x7fffffffLL, "input larger than 2 GiB (32-bit buffer offsets)");
   // at most 32 tiles (8² at batch 8): 32-tile × 64-channel workgroups (ops.wino_conv's planner
   // mirrors this rule)
   const bool wide = ntiles <= 32 && K % 64 == 0;
   const int mt = wide ? 32 : kMT;
   const int ntb = (int)((ntiles + mt - 1) / mt), nkb = K / (wide ? 64 : kNC);
-  SKP_CHECK_ARG((long long)ntb * nkb * nsplit <= 0x7fffffffLL, "grid too large");
+  if (!err && (long long)ntb * nkb * nsplit > kMaxGrid) err = "grid too large";
+  SKP_CHECK_ARG(!err, err);
   // one channel block's U slice is C·32·36·4 B; keep all of U on an L2 slice when it fits
   const long long ubytes = (long long)K * C * kP * 4;
   const int kb_major = ubytes > (2LL << 20);
-  const int epi = nsplit > 1 ? 0 : (bias ? 1 : 0) | (residual ? 2 : 0);
-  float* out = nsplit > 1 ? ws : y;
-  const int dbg = SKP_WINO_DEBUG;
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(ntb * nkb * nsplit));
-#define SKP_WG(E)                                                                                                    \
-  if (wide)                                                                                                          \
-    hipLaunchKernelGGL((wino_f4_kernel<E, 32>), grid, dim3(kThreads), 0, st, x, U, bias, residual, out, B, C, K, H, W, \
-                       tw, tpi, (int)ntiles, ntb, nkb, kb_major, C / nsplit, dbg);                                    \
-  else                                                                                                               \
-    hipLaunchKernelGGL((wino_f4_kernel<E, 64>), grid, dim3(kThreads), 0, st, x, U, bias, residual, out, B, C, K, H, W, \
-                       tw, tpi, (int)ntiles, ntb, nkb, kb_major, C / nsplit, dbg)
-  switch (epi) {
-    case 0: SKP_WG(0); break;
-    case 1: SKP_WG(1); break;
-    case 2: SKP_WG(2); break;
-    default: SKP_WG(3); break;
-  }
-#undef SKP_WG
-  SKP_LAUNCH_CHECK();
-  if (nsplit > 1) return splitk_reduce(ws, nsplit, B, K, H * W, bias, residual, y, st);
-  return SKP_OK;
+  return conv_launch(__func__, bias, residual, y, ws, nsplit, B, K, H * W, SKP_WINO_DEBUG, false, st,
+                     [&](int epi, float* out, int dbg) {
+                       const auto kernel = with_epi<4>(
+                           epi, [&](auto E) { return wide ? wino_f4_kernel<E(), 32> : wino_f4_kernel<E(), 64>; });
+                       hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, x, U, bias, residual, out, B, C, K, H, W, tw,
+                                          tpi, (int)ntiles, ntb, nkb, kb_major, C / nsplit, dbg);
+                     });
 }
 
 // ================================================================================================
 // Winograd F(4×4, 3×3), region-staged version for H and W multiples of 32 (every VAE-encoder
-// layer at 512² input and the UNet's 64² / 32² layers).
+// layer at 512² input and the UNet's 64² / 32² layers) and for 16×16 images.
 //
 // The kernel above is bound by its one-deep pipeline: every stage waits for LDS-DMA it issued
 // in the same stage (≈1 µs under load, about one stage of MFMA work), and with neither
-// transforms nor MFMAs it still takes half its time.  This one keeps three stages in flight:
-//   - a workgroup owns an 8×8 block of output tiles (32×32 pixels) × 32 output channels; per
-//     stage of 4 input channels it DMAs the block's 34×34-pixel input region as rows of ten
-//     16-byte chunks (columns x0-4 … x0+35; rows and chunks outside the image load as zeros —
-//     out-of-range buffer offsets — so the zero padding costs no masking) and the stage's U
-//     slice, into 3-slot LDS rings, two stages ahead of use;
+// transforms nor MFMAs it still takes half its time.  This one keeps its loads a stage or two
+// ahead of use:
+//   - a workgroup of 4 waves owns a half-height block of 8 × 4 output tiles (32 × 16 pixels) × 32
+//     output channels; its LDS (76 KB at most) leaves room for a second workgroup on the CU, so one's
+//     prologue / epilogue overlaps the other's stage loop.  Per stage of 4 input channels it DMAs
+//     the block's 18-row × 40-pixel input region as rows of ten 16-byte chunks (columns x0-4 …
+//     x0+35; rows and chunks outside the image load as zeros — out-of-range buffer offsets — so
+//     the zero padding costs no masking) and the stage's U slice into LDS rings: the raw input
+//     into 3 slots, two stages ahead of use (it streams from HBM), the weights into 2 slots, one
+//     stage ahead (every tile block re-reads them and they hit L2).  The 16×16 geometry (two whole
+//     images per workgroup) and the V-staged form differ in the rings only, see wino2_body;
 //   - the transformed input never goes through LDS: lane (tile, channel) of a wave reads its
 //     own 6×6 patch (three ds_read_b128 per row) and computes the V values that are exactly its
-//     MFMA A operand.  The two waves of a SIMD (w, w+4) share the 16 tiles and split the 36
-//     positions by transform rows (0-2 / 3-5), so no transform work is repeated: each runs half
-//     of the column pass and half of the row pass;
+//     MFMA A operand.  Partner waves w and w+2 share 16 tiles and split the 36 positions by
+//     transform rows (0-2 / 3-5), so no transform work is repeated: each runs half of the column
+//     pass and half of the row pass;
 //   - a wave owns 16 tiles × 32 channels × 18 positions (2 MFMA blocks, 144 accumulators) and
 //     transforms stage s+1 while its MFMAs run on stage s (the A operands are double-buffered
 //     in registers);
-//   - one barrier per stage; the epilogue applies the output transform to each half's rows and
-//     the partner waves exchange the half-sums through LDS (two rounds of 8 KB per wave).
+//   - one barrier per stage; the epilogue applies the output transform to each half's rows, the
+//     partner waves add their halves in LDS planes (16 channels at a time) and every thread then
+//     stores whole rows.
 // ================================================================================================
 namespace {
 namespace w2 {
 
 constexpr int kNC = 32;                    // output channels per workgroup
 constexpr int kCK = 4;                     // input channels per stage
-// Block geometry: a workgroup's 64 output tiles are TXB×TXB tiles of each of NI images' regions.
-//   TXB 8: a 32×32-pixel block of one image (H, W multiples of 32); region 34 rows × 10 chunks
-//   TXB 4: four whole 16×16 images; region 18 rows × 6 chunks per image
-// The channel stride (floats) makes the patch reads' ds_read_b128 lane groups conflict-free.
+constexpr int kNW = 4;                     // waves per workgroup: halves 0 / 1 = waves 0-1 / 2-3
+// Block geometry: a workgroup's 32 output tiles are NI images' regions of RR rows × RC 16-byte chunks.
+//   TXB 8: a half-height block, 8 × 4 tiles = 32 × 16 pixels of one image (H, W multiples of 32);
+//          region 18 rows × 10 chunks
+//   TXB 4: two whole 16×16 images (4 × 4 tiles each); region 18 rows × 6 chunks per image
+// The channel stride CHF (floats) makes the patch reads' ds_read_b128 lane groups conflict-free:
+// CHF/4 ≡ 0 (TXB 8), 12 (TXB 4) mod 16.
 template <int TXB>
-struct Geo;
+struct GeoN;
 template <>
-struct Geo<8> {
-  static constexpr int NI = 1, RR = 34, RC = 10, CHF = 1408;
+struct GeoN<8> {
+  static constexpr int NI = 1, RR = 18, RC = 10, CHF = 768;
 };
 template <>
-struct Geo<4> {
-  static constexpr int NI = 4, RR = 18, RC = 6, CHF = 1744;
-};
-// NW = 4 with TXB 8: a half-height block (8 × 4 tiles = 32 × 16 pixels, 4 waves), so that two
-// workgroups share a CU and one's prologue / epilogue overlaps the other's stage loop
-template <int TXB, int NW>
-struct GeoN : Geo<TXB> {};
-template <>
-struct GeoN<8, 4> {
-  static constexpr int NI = 1, RR = 18, RC = 10, CHF = 768;   // same bank residues as 1408
-};
-// NW = 4 with TXB 4: two whole 16×16 images per workgroup (4 waves); CHF/4 ≡ 12 (mod 16) keeps
-// the patch reads' ds_read_b128 lane groups conflict-free like 1744 (≡ 4)
-template <>
-struct GeoN<4, 4> {
+struct GeoN<4> {
   static constexpr int NI = 2, RR = 18, RC = 6, CHF = 880;
 };
-template <int TXB, int NW = 8>
-struct GeoT : GeoN<TXB, NW> {
-  using GeoN<TXB, NW>::NI;
-  using GeoN<TXB, NW>::RR;
-  using GeoN<TXB, NW>::RC;
-  using GeoN<TXB, NW>::CHF;
+template <int TXB>
+struct GeoT : GeoN<TXB> {
+  using GeoN<TXB>::NI;
+  using GeoN<TXB>::RR;
+  using GeoN<TXB>::RC;
+  using GeoN<TXB>::CHF;
   static constexpr int RF = 4 * RC;                                   // floats per region row
   static constexpr int RAWF = (4 * CHF + 255) / 256 * 256;            // raw slot, whole 1-KB chunks
   static constexpr int RAW_INSTR = RAWF / 256;
@@ -554,61 +636,17 @@ constexpr int kUP2 = 28;
 constexpr int kUF2 = kCK * kNC * kUP2;     // 3584 floats = 14 KB per U slot
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 static_assert(kUF % 256 == 0 && kUF2 % 256 == 0, "whole 1-KB chunks");
-static_assert((4 * GeoT<8>::RAWF + 3 * kUF) * 4 <= 160 * 1024 && 3 * (GeoT<4>::RAWF + kUF) * 4 <= 160 * 1024, "LDS");
-static_assert(2 * 8 * 1024 <= kUF * 4, "epilogue exchange: two waves' 8 KB per ring buffer");
+static_assert((3 * GeoT<8>::RAWF + 2 * kUF) * 4 <= 80 * 1024 && 2 * (GeoT<4>::RAWF + kUF) * 4 <= 80 * 1024,
+              "rings of two workgroups per CU");
 
-// Bᵀ (rows i = transform row, columns a = patch row) for the points (0, 1, -1, 1/2, -2, ∞)
-__device__ constexpr float kBt[6][6] = {{1.f, -1.5f, -2.f, 1.5f, 1.f, 0.f},  {0.f, -1.f, 0.5f, 2.5f, 1.f, 0.f},
-                                        {0.f, 1.f, -2.5f, 0.5f, 1.f, 0.f},  {0.f, -2.f, -1.f, 2.f, 1.f, 0.f},
-                                        {0.f, 0.5f, -1.f, -0.5f, 1.f, 0.f}, {0.f, 1.f, -1.5f, -2.f, 1.5f, 1.f}};
 // Aᵀ (4 outputs × 6 positions)
 __device__ constexpr float kAt[4][6] = {{1.f, 1.f, 1.f, 1.f, 1.f, 0.f},
                                         {0.f, 1.f, -1.f, 0.5f, -2.f, 0.f},
                                         {0.f, 1.f, 1.f, 0.25f, 4.f, 0.f},
                                         {0.f, 1.f, -1.f, 0.125f, -8.f, 1.f}};
 
-#ifndef SKP_W2_PACKED
-#define SKP_W2_PACKED 1   // 0: the scalar half_transform (A/B build)
-#endif
-#if SKP_W2_PACKED
-#define W2_TRANSFORM half_transform_pk
-#else
-#define W2_TRANSFORM half_transform
-#endif
-
 // s_waitcnt vmcnt(n) with expcnt / lgkmcnt left alone (gfx9 encoding)
 #define W2_VMCNT(n) __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | (7 << 4) | (15 << 8))
-
-// Transform rows 3H..3H+2 of V = Bᵀ d B for this lane's patch (region rows at `raw`, the
-// patch's first row; columns: .w of chunk 0, chunk 1, .x of chunk 2) → a[18] = V[3H+ii][j].
-template <int H, int RF>
-__device__ __forceinline__ void half_transform(const float* raw, float* a) {
-  float t[3][6];
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    const float4 c0 = *reinterpret_cast<const float4*>(raw + r * RF);
-    const float4 c1 = *reinterpret_cast<const float4*>(raw + r * RF + 4);
-    const float4 c2 = *reinterpret_cast<const float4*>(raw + r * RF + 8);
-    const float d[6] = {c0.w, c1.x, c1.y, c1.z, c1.w, c2.x};
-#pragma unroll
-    for (int ii = 0; ii < 3; ++ii) {
-      const float c = kBt[3 * H + ii][r];
-      if (c == 0.0f) continue;
-      bool first = true;   // the first nonzero coefficient of row 3H+ii (compile time)
-#pragma unroll
-      for (int rp = 0; rp < r; ++rp)
-        if (kBt[3 * H + ii][rp] != 0.0f) first = false;
-#pragma unroll
-      for (int b = 0; b < 6; ++b)
-        t[ii][b] = first ? ((c == 1.0f) ? d[b] : c * d[b]) : ((c == 1.0f) ? t[ii][b] + d[b] : fmaf(c, d[b], t[ii][b]));
-    }
-    // keep chunks 0 and 2 whole: with one component used the compiler narrows them to
-    // ds_read_b32, 4-way bank-conflicted at this layout (ds_read_b128 is conflict-free)
-    asm volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c0.z), "v"(c2.y), "v"(c2.z), "v"(c2.w));
-  }
-#pragma unroll
-  for (int ii = 0; ii < 3; ++ii) bt6(t[ii][0], t[ii][1], t[ii][2], t[ii][3], t[ii][4], t[ii][5], a + 6 * ii, 1);
-}
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -624,12 +662,14 @@ __device__ __forceinline__ void bt6_shared(T a0, T a1, T a2, T a3, T a4, T a5, T
   y[5] = __builtin_elementwise_fma((T)1.5f, e, __builtin_elementwise_fma((T)-2.0f, f, a5 - a1));
 }
 
-// Packed form of half_transform (v_pk_* f32): the column pass runs on column pairs
+// Transform rows 3H..3H+2 of V = Bᵀ d B for this lane's patch (region rows at `raw`, the patch's
+// first row; columns: .w of chunk 0, chunk 1, .x of chunk 2) → a[18] = V[3H+ii][j], on the packed
+// f32 VALU (v_pk_*): the column pass runs on column pairs
 // (1,2), (3,4), (0,5) — the first two are halves of the middle 16-B chunk, the third one
 // v_pk_mov per row — streaming the patch rows through shared differences (9 / 7 operations
 // per pair for rows 0-2 / 3-5 instead of 10); the row pass packs transform rows 3H and 3H+1
 // (pairs re-formed per column) and runs row 3H+2 unpacked, both with the shared-difference
-// Bᵀ.  ≈80 VALU instructions per patch half and stage instead of ≈109.
+// Bᵀ.  ≈80 VALU instructions per patch half and stage (≈109 unpacked).
 template <int H, int RF>
 __device__ __forceinline__ void half_transform_pk(const float* raw, float* a) {
   f2 t[3][3];   // t[ii][p]: column pair p of transform row 3H+ii
@@ -670,6 +710,8 @@ __device__ __forceinline__ void half_transform_pk(const float* raw, float* a) {
         if (r == 5) t[2][p] = k3[p] + d[p];
       }
     }
+    // keep chunks 0 and 2 whole: with one component used the compiler narrows them to
+    // ds_read_b32, 4-way bank-conflicted at this layout (ds_read_b128 is conflict-free)
     asm volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c0.z), "v"(c2.y), "v"(c2.z), "v"(c2.w));
   }
   // row pass: column b of row ii is t[ii][0] = (b1, b2), t[ii][1] = (b3, b4), t[ii][2] = (b0, b5)
@@ -731,7 +773,7 @@ __device__ __forceinline__ void s2_transform(const float* raw, float* a) {
     d[i][2] = c1.z;
     d[i][3] = c1.w;
     d[i][4] = c2.x;
-    // keep chunk 2 whole (see half_transform)
+    // keep chunk 2 whole (see half_transform_pk)
     asm volatile("" ::"v"(c2.y), "v"(c2.z), "v"(c2.w));
   }
 #pragma unroll
@@ -768,7 +810,7 @@ __device__ __forceinline__ void s2_output(const float* m, float* y) {
 }  // namespace w2
 
 struct W2Smem {
-  float *R0, *R1, *R2, *R3, *U0, *U1, *U2;
+  float *R0, *R1, *R2, *U0, *U1, *U2;   // ring slots; a form without a slot passes nullptr
 };
 
 // s_waitcnt vmcnt(n) for a wave-uniform n (the per-wave DMA instruction counts differ)
@@ -794,12 +836,13 @@ __device__ __forceinline__ void w2_vmcnt(int n) {
   }
 }
 
-#ifndef SKP_W2_RS4
-#define SKP_W2_RS4 0   // 1: four raw-input slots for the 32×32 geometry (lead 3; measured 1-2% slower)
-#endif
-
 // One wave's whole program for transform half HH (rows 3HH..3HH+2); the kernel branches once
 // on the wave's half so the stage loop is straight-line code for each.
+//
+// Rings: TXB 8 (and its S2 form) a raw-input ring of 3 slots (R0-R2, lead 2: the input streams
+// from HBM) and a weight ring of 2 (U0, U1, lead 1: every tile block re-reads the weights, which
+// hit L2); TXB 4 a raw ring of 2 (R0, R1) and a weight ring of 2; VST no raw ring and a weight ring
+// of 3 (below).  Every form leaves room for a second workgroup on the CU.
 //
 // VST (the V-staged form, skp_conv3x3_wino2_v): `x` is not the image but its transform V from
 // skp_wino2_vtransform, one 18-KB slab [wave][chunk][lane] per (half-height block, stage): lane L
@@ -813,36 +856,34 @@ __device__ __forceinline__ void w2_vmcnt(int n) {
 // S2 (the stride-2 form, skp_conv3x3s2_f2): the same staging, rings and barriers; each tile's 5×5
 // sub-patch gives a 2×2 tile of the (H/2, W/2) output from 25 products (s2_transform above), U
 // rows are 28 floats (14 KB per slot) and the epilogue exchanges 8 × 16-pixel planes.
-template <int EPI, int HH, int TXB, int NW, bool VST = false, bool S2 = false>
+template <int EPI, int HH, int TXB, bool VST = false, bool S2 = false>
 __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __restrict__ x, const float* __restrict__ U,
                                            const float* __restrict__ bias, const float* __restrict__ res,
                                            float* __restrict__ y, int C, int K, int H, int W, int img, int x0,
                                            int y0, int kb, int c0, int csplit, int wv, int dbg,
                                            float2* __restrict__ gnp) {
-  using Geo = w2::GeoT<TXB, NW>;
+  using Geo = w2::GeoT<TXB>;
+  constexpr int NW = w2::kNW;
   constexpr int kChF = Geo::CHF, kRowF = Geo::RF, kRawInstr = Geo::RAW_INSTR, NI = Geo::NI, RR = Geo::RR,
                 RC = Geo::RC;
-  static_assert(!S2 || (TXB == 8 && NW == 4 && !VST && (EPI & ~1) == 0), "stride-2 form: half-height blocks, bias only");
+  static_assert(!S2 || (TXB == 8 && !VST && (EPI & ~1) == 0), "stride-2 form: half-height blocks, bias only");
   constexpr int kUP = S2 ? w2::kUP2 : w2::kUP, kUF = S2 ? w2::kUF2 : w2::kUF, kUInstr = kUF / 256;
   constexpr int NP = S2 ? (HH ? 10 : 15) : 18;   // positions of this half
   constexpr int kInstr = kRawInstr + kUInstr;
   constexpr int kMaxRaw = (kRawInstr + NW - 1) / NW;
   constexpr int kMaxU = (kUInstr + NW - 1) / NW + 1;
   constexpr int NT = NW * WAVE;
-  // weight ring: 3 slots (lead 2) with 8 waves; 2 (lead 1) in the half-height form, whose LDS must
-  // leave room for a second workgroup on the CU
-  constexpr int US = NW == 4 ? 2 : 3;
-  // raw-input ring of RS slots (lead RS − 1 stages: the input streams from HBM), weight ring
-  // of 3 (lead 2: the weights are re-read by every tile block and hit L2)
-  static_assert(!VST || (TXB == 8 && NW == 4), "V-staged form: half-height blocks of 4 waves");
-  constexpr int RS = (VST || (TXB == 4 && NW == 4)) ? 2 : (TXB == 8 && NW == 8 && SKP_W2_RS4) ? 4 : 3;
+  static_assert(!VST || TXB == 8, "V-staged form: half-height blocks");
+  // raw-input ring of RS slots (lead RS − 1 stages); VST has none, RS = 2 there only picks the
+  // epilogue's third plane buffer
+  constexpr int RS = (VST || TXB == 4) ? 2 : 3;
   float *R0 = sm.R0, *R1 = sm.R1, *R2 = sm.R2, *U0 = sm.U0, *U1 = sm.U1, *U2 = sm.U2;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wm = wv % (NW / 2);
   const size_t plane = (size_t)H * W;
   const size_t ximg = (size_t)img * C * plane;
 
-  // this wave's DMA chunks of a stage: chunk g = wv + 8m (the raw slot's chunks, then U's 20);
+  // this wave's DMA chunks of a stage: chunk g = wv + 4m (the raw slot's chunks, then U's);
   // raw chunk → (channel, image of the block, region row, 16-B column chunk)
   unsigned voff[kMaxRaw];
   int nraw = 0;
@@ -864,18 +905,19 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   }
   const int nuw = (kInstr - 1 - wv) / NW + 1 - nraw;  // U chunks of this wave
   const int ufirst = wv + NW * nraw - kRawInstr;      // its first U chunk
-  // vmcnt allowances (in-order counter; per step the wave issues U(s+2) then raw(s+RS)):
-  // top of step s needs U(s) and raw(s+1) landed; the prologue needs raw(0)
-  // (US = 2: per step U(s+1) then raw(s+3); the top of step s needs U(s) and raw(s+1), the prologue raw(0))
-  // (RS = 2, US = 2: per step U(s+1) then raw(s+2), the top of step s waits for both of the
-  // previous step's; the prologue issues raw(0), U(0), raw(1) and waits for raw(0))
-  const int allow_step = RS == 2 ? 0 : US == 2 ? nraw : RS == 4 ? nuw + 2 * nraw : nuw + nraw;
-  const int allow_pro = RS == 2 ? nuw + nraw : US == 2 ? nuw + 2 * nraw : RS == 4 ? 2 * nuw + 3 * nraw : 2 * nuw + 2 * nraw;
+  // vmcnt allowances (in-order counter).  The top of step s needs U(s) and raw(s+1) landed, the
+  // prologue raw(0).
+  // RS = 3: per step the wave issues U(s+1) then raw(s+3), so raw(s+2) may stay in flight at the
+  //   top of step s; the prologue issues raw(0), U(0), raw(1), raw(2).
+  // RS = 2: per step U(s+1) then raw(s+2), and the top of step s waits for both of the previous
+  //   step's; the prologue issues raw(0), U(0), raw(1).
+  const int allow_step = RS == 2 ? 0 : nraw;
+  const int allow_pro = RS == 2 ? nuw + nraw : nuw + 2 * nraw;
   const size_t xend = (size_t)(img + NI) * C * plane; // the buffer ends with the block's last image
   const float* Ub = U + ((size_t)kb * C + c0) * w2::kNC * kUP;
   const int nst = csplit / w2::kCK;
 
-  // raw(t) → raw slot t % RS, U(t) → U slot t % 3
+  // raw(t) → raw slot t % RS, U(t) → U slot t % 2 (VST: t % 3)
   auto issue_raw = [&](int t, float* rs_lds) {
     const bool ok = t < nst;
     const size_t off = ((size_t)c0 + (size_t)(ok ? t : 0) * w2::kCK) * plane;
@@ -940,7 +982,7 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   // the lane's patch of a raw slot → its A operands
   auto transform = [&](const float* raw, float (&an)[NP]) {
     if constexpr (S2) w2::s2_transform<HH, kRowF>(raw + roff, an);
-    else w2::W2_TRANSFORM<HH, kRowF>(raw + roff, an);
+    else w2::half_transform_pk<HH, kRowF>(raw + roff, an);
   };
 
   if constexpr (VST) {
@@ -1028,25 +1070,23 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
       vstep(s0 + 2, A2, U2, A1, U1);
     }
   } else {
-    // prologue: the DMAs of "steps" −RS..−1 (raw(0..RS−1), U(0), U(1)) in step order; wait for
+    // prologue: the DMAs of "steps" −RS..−1 (raw(0..RS−1), U(0)) in step order; wait for
     // raw(0) and transform it
     issue_raw(0, R0);
-    if (RS == 4) issue_raw(1, R1);
     issue_u(0, U0);
-    if (RS >= 3) issue_raw(RS - 2, RS == 4 ? R2 : R1);
-    if (US == 3 && nst > 1) issue_u(1, U1);
-    issue_raw(RS - 1, RS == 4 ? sm.R3 : RS == 3 ? R2 : R1);
+    issue_raw(1, R1);
+    if (RS == 3) issue_raw(2, R2);
     w2_vmcnt(nst > 1 ? allow_pro : 0);
     __syncthreads();
     transform(R0, a0);
 
-    // stage s: wait for U(s) and raw(s+1); barrier; issue U(s+2) and raw(s+RS) into the slots
+    // stage s: wait for U(s) and raw(s+1); barrier; issue U(s+1) and raw(s+RS) into the slots
     // freed by stage s-1; transform raw(s+1) (slot (s+1)%RS) and run the MFMAs on U(s) (slot
-    // s%3).  The SIMD partners (waves w, w+4: the two halves) do these in opposite orders.
+    // s%2).  The partner waves w, w+2 (the two halves) do these in opposite orders.
     auto step = [&](int s, float* Rn, float* Us, float* Ri, float* Ui, const float (&acur)[NP], float (&anext)[NP]) {
       w2_vmcnt(s + 1 < nst ? allow_step : 0);
       __syncthreads();
-      if (s + US - 1 < nst) issue_u(s + US - 1, Ui);
+      if (s + 1 < nst) issue_u(s + 1, Ui);
       issue_raw(s + RS, Ri);   // past the last stage: empty (zero-length) loads keep the counts
       const bool tr = s + 1 < nst && !(dbg & 1);
       if (HH == 0) {
@@ -1057,17 +1097,19 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
         if (tr) transform(Rn, anext);
       }
     };
-    // unrolled by lcm(RS, 3, 2): raw slot s%RS, U slot s%3, A-operand buffer s%2
-    constexpr int PER = RS == 4 ? 12 : RS == 2 ? 2 : 6;
-    float* const Rsl[4] = {R0, R1, R2, sm.R3};
-    float* const Usl[3] = {U0, U1, U2};
+    // unrolled by lcm(RS, 2): raw slot s%RS, U slot and A-operand buffer s%2
+    constexpr int PER = RS == 2 ? 2 : 6;
+    // (the table keeps a fourth, unused entry: with three the compiler allocates the TXB 8 stage
+    // loop's registers differently, and this code is held to its measured instruction stream)
+    float* const Rsl[4] = {R0, R1, R2, nullptr};
+    float* const Usl[2] = {U0, U1};
     for (int s0 = 0; s0 < ((dbg & 16) ? 0 : nst); s0 += PER) {
-      step(s0, Rsl[1 % RS], Usl[0], Rsl[0], Usl[US - 1], a0, a1);
+      step(s0, Rsl[1], Usl[0], Rsl[0], Usl[1], a0, a1);
   #pragma unroll
       for (int j = 1; j < PER; ++j) {
         if (s0 + j < nst) {
-          if ((j & 1) == 0) step(s0 + j, Rsl[(j + 1) % RS], Usl[j % US], Rsl[j % RS], Usl[(j + US - 1) % US], a0, a1);
-          else step(s0 + j, Rsl[(j + 1) % RS], Usl[j % US], Rsl[j % RS], Usl[(j + US - 1) % US], a1, a0);
+          if ((j & 1) == 0) step(s0 + j, Rsl[(j + 1) % RS], Usl[j % 2], Rsl[j % RS], Usl[(j + 1) % 2], a0, a1);
+          else step(s0 + j, Rsl[(j + 1) % RS], Usl[j % 2], Rsl[j % RS], Usl[(j + 1) % 2], a1, a0);
         }
       }
     }
@@ -1076,7 +1118,7 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
 
   // epilogue: lane holds tiles 4(lane>>4)+r of the wave's 16 (ty = 2wm + (lane>>5),
   // tx = 4((lane>>4)&1) + r) × channel 16 blk + (lane&15), rows 3HH..3HH+2 of M.  Per block of 16
-  // channels: the other half's waves stage their partial tiles in LDS ([ch][32 rows][32 px]),
+  // channels: the other half's waves stage their partial tiles in LDS ([ch][16 rows][32 px]),
   // this half's waves add theirs in place, then every thread stores whole 128-B rows.
   W2_VMCNT(0);
   __syncthreads();
@@ -1137,9 +1179,9 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
       if (blk == 0) __syncthreads();
     }
   } else {
-    // channel c of a block: a 32×32-float plane in R0/R1/R2/U0 (four channels each, skewed by 16
+    // channel c of a block: a 512-float plane in R0/R1/R2/U0 (four channels each, skewed by 16
     // floats per buffer so the 8-lane store groups hit distinct banks)
-    constexpr int PH = (TXB == 8 && NW == 4) ? 16 : 32;   // plane rows (TXB 8: the block's pixel rows)
+    constexpr int PH = 16;   // TXB 8: plane rows = the block's pixel rows
     // plane stride: TXB 8 the block's PH × 32 pixels, TXB 4 its NI 16×16 images (+4 skew); with a
     // 2-slot raw ring the third plane buffer is U1 (no R2)
     constexpr int PLS = (TXB == 8 ? PH * 32 : NI * 256) + 4;
@@ -1148,8 +1190,8 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
       float* b = (c >> 2) == 0 ? R0 : (c >> 2) == 1 ? R1 : (c >> 2) == 2 ? P2 : U0;
       return b + (c & 3) * PLS + (c >> 2) * 16;
     };
-    // this lane's output tile row within the 1024-float plane: TXB 8: tiles (2wm + lane>>5, 4((lane>>4)&1)
-    // + r) of the 32×32 block; TXB 4: image wm (256 floats), tile row lane>>4, tiles r = 0..3
+    // this lane's output tile row within the plane: TXB 8: tiles (2wm + lane>>5, 4((lane>>4)&1)
+    // + r) of the 32×16 block; TXB 4: image wm (256 floats), tile row lane>>4, tiles r = 0..3
     float* pl = plane_of(lane & 15);
     const int pbase = TXB == 8 ? (4 * (2 * wm + (lane >> 5))) * 32 + 4 * (4 * ((lane >> 4) & 1))
                                : wm * 256 + (4 * (lane >> 4)) * 16;
@@ -1186,8 +1228,8 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
         }
       }
       __syncthreads();
-      // 16 channels × 1024 floats in 16-B chunks; a wave instruction = 1 KB of one channel:
-      // TXB 8: 8 whole rows of the 32×32 block; TXB 4: one whole 16×16 image plane
+      // 16 channels × 512 floats in 16-B chunks; a wave instruction = 1 KB of one channel:
+      // TXB 8: 8 whole rows of the 32×16 block; TXB 4: one whole 16×16 image plane
       constexpr int PCF = TXB == 8 ? PH * 8 : NI * 64;   // float4 per channel plane
       constexpr int NIT = 16 * PCF / NT;                  // wave instructions per wave
       // TXB 8: wave w takes wave instructions 8w … 8w + 7 (1 KB = 8 rows of one channel each), so
@@ -1275,19 +1317,19 @@ __device__ __forceinline__ void wino2_body(const W2Smem& sm, const float* __rest
   }
 }
 
-template <int EPI, int TXB, int NW = 8, bool S2 = false>
-__global__ __launch_bounds__(NW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino2_kernel(
+template <int EPI, int TXB, bool S2 = false>
+__global__ __launch_bounds__(w2::kNW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino2_kernel(
     const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ res, float* __restrict__ y, int nimg, int C, int K, int H, int W, int bw, int bpi,
     int nblk, int nkb, int kb_major, int csplit, int dbg, float2* __restrict__ gnp) {
   // separate LDS objects per ring slot: the compiler tells a DMA into one slot from a ds_read of
   // another and does not wait for outstanding DMAs before every LDS read
-  __shared__ __attribute__((aligned(16))) float R0[w2::GeoT<TXB, NW>::RAWF], R1[w2::GeoT<TXB, NW>::RAWF],
-      R2[(TXB == 4 && NW == 4) ? 4 : w2::GeoT<TXB, NW>::RAWF],
-      R3[(TXB == 8 && NW == 8 && SKP_W2_RS4) ? w2::GeoT<TXB, NW>::RAWF : 4];
+  // (TXB 4 has no third raw slot: its R2 is an unused stub that the compiler drops)
+  constexpr int RAWF = w2::GeoT<TXB>::RAWF;
+  __shared__ __attribute__((aligned(16))) float R0[RAWF], R1[RAWF], R2[TXB == 4 ? 4 : RAWF];
   constexpr int UF = S2 ? w2::kUF2 : w2::kUF;
-  __shared__ __attribute__((aligned(16))) float U0[UF], U1[UF], U2[NW == 4 ? 4 : UF];
-  // workgroup → (input-channel split, 32×32-pixel block, channel block); consecutive logical ids
+  __shared__ __attribute__((aligned(16))) float U0[UF], U1[UF];
+  // workgroup → (input-channel split, half-height block, channel block); consecutive logical ids
   // share one XCD.  A split sums its csplit input channels into slab sp of y (the workspace).
   const int G = gridDim.x;
   const int g = blockIdx.x;
@@ -1303,51 +1345,23 @@ __global__ __launch_bounds__(NW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)
     tb = L / nkb;
     kb = L - tb * nkb;
   }
-  // TXB 8: block = 32×32 pixels of one image; TXB 4: images 4tb..4tb+3 whole
+  // TXB 8: block = 32×16 pixels of one image; TXB 4: images 2tb, 2tb+1 whole
   int img, x0 = 0, y0 = 0;
   if (TXB == 8) {
     img = tb / bpi;
     const int br = tb - img * bpi;
     const int by = br / bw;
     x0 = 32 * (br - by * bw);
-    y0 = (NW == 4 ? 16 : 32) * by;
+    y0 = 16 * by;
   } else {
-    img = (NW == 4 ? 2 : 4) * tb;
+    img = 2 * tb;
   }
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const W2Smem sm{R0, R1, R2, R3, U0, U1, U2};
+  const W2Smem sm{R0, R1, R2, U0, U1, nullptr};
   const int c0 = sp * csplit;
-  if (wv < NW / 2)
-    wino2_body<EPI, 0, TXB, NW, false, S2>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
-  else wino2_body<EPI, 1, TXB, NW, false, S2>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
-}
-
-// U2[kb][c][k%32][40]: positions 0..17 at 0..17, 18..35 at 20..37, the rest zero
-__global__ void wino2_weights_kernel(const float* __restrict__ w, int K, int C, int flip, float* __restrict__ U) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i >= (long long)K * C) return;
-  const int k = (int)(i / C), c = (int)(i - (long long)k * C);
-  double g[9];
-  for (int u = 0; u < 3; ++u)
-    for (int v = 0; v < 3; ++v)
-      g[3 * u + v] = flip ? (double)w[((size_t)c * K + k) * 9 + (2 - u) * 3 + (2 - v)]
-                          : (double)w[((size_t)k * C + c) * 9 + u * 3 + v];
-  const double Gm[6][3] = {{1.0, 0.0, 0.0},
-                           {1.0 / 3, 1.0 / 3, 1.0 / 3},
-                           {-1.0 / 3, 1.0 / 3, -1.0 / 3},
-                           {-16.0 / 15, -8.0 / 15, -4.0 / 15},
-                           {1.0 / 15, -2.0 / 15, 4.0 / 15},
-                           {0.0, 0.0, 1.0}};
-  double t[6][3];
-  for (int a = 0; a < 6; ++a)
-    for (int v = 0; v < 3; ++v) t[a][v] = Gm[a][0] * g[v] + Gm[a][1] * g[3 + v] + Gm[a][2] * g[6 + v];
-  float* out = U + (((size_t)(k / w2::kNC) * C + c) * w2::kNC + (k % w2::kNC)) * w2::kUP;
-  for (int p = 0; p < w2::kUP; ++p) out[p] = 0.0f;
-  for (int a = 0; a < 6; ++a)
-    for (int b = 0; b < 6; ++b) {
-      const int p = 6 * a + b;
-      out[p < 18 ? p : p + 2] = (float)(t[a][0] * Gm[b][0] + t[a][1] * Gm[b][1] + t[a][2] * Gm[b][2]);
-    }
+  if (wv < w2::kNW / 2)
+    wino2_body<EPI, 0, TXB, false, S2>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
+  else wino2_body<EPI, 1, TXB, false, S2>(sm, x, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
 }
 
 // The stride-2 form's U = Gs2 g Gs2ᵀ, Gs2 = [1 0 0; 1 0 1; 0 0 1; 0 1 0; 0 1 0], in fp64 → fp32:
@@ -1371,10 +1385,10 @@ __global__ void wino2s2_weights_kernel(const float* __restrict__ w, int K, int C
     }
 }
 
-// The V-staged form of wino2_kernel<EPI, 8, 4>: half-height blocks, 4 waves, V in registers and a
+// The V-staged form of wino2_kernel<EPI, 8>: half-height blocks, 4 waves, V in registers and a
 // three-slot U ring of 20 KB each (60 KB: two workgroups per CU); grid order as wino2_kernel.
 template <int EPI>
-__global__ __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino2v_kernel(
+__global__ __launch_bounds__(w2::kNW * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino2v_kernel(
     const float* __restrict__ V, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ res, float* __restrict__ y, int nimg, int C, int K, int H, int W, int bw, int bpi,
     int nblk, int nkb, int kb_major, int csplit, int dbg, float2* __restrict__ gnp) {
@@ -1402,11 +1416,11 @@ __global__ __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))
   const int by = br / bw;
   const int x0 = 32 * (br - by * bw), y0 = 16 * by;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const W2Smem sm{U0 + w2::kUF / 2, U1 + w2::kUF / 2, nullptr, nullptr, U0, U1, U2};
+  const W2Smem sm{U0 + w2::kUF / 2, U1 + w2::kUF / 2, nullptr, U0, U1, U2};
   const int c0 = sp * csplit;
-  if (wv < 2)
-    wino2_body<EPI, 0, 8, 4, true>(sm, V, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
-  else wino2_body<EPI, 1, 8, 4, true>(sm, V, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
+  if (wv < w2::kNW / 2)
+    wino2_body<EPI, 0, 8, true>(sm, V, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
+  else wino2_body<EPI, 1, 8, true>(sm, V, U, bias, res, y, C, K, H, W, img, x0, y0, kb, c0, csplit, wv, dbg, gnp);
 }
 
 // V = Bᵀ d B of every (image, channel, 4×4 tile) once, d = x or act(GroupNorm(x + shift)) with the
@@ -1422,7 +1436,7 @@ __global__ __launch_bounds__(4 * WAVE) void wino2_vtransform_kernel(
     const float* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ shift, int G, float* __restrict__ V, int C, int H, int W,
     int bw, int bpi) {
-  using Geo = w2::GeoT<8, 4>;
+  using Geo = w2::GeoT<8>;
   constexpr int RR = Geo::RR, RC = Geo::RC, kChF = Geo::CHF, kRowF = Geo::RF;
   __shared__ __attribute__((aligned(16))) float R[Geo::RAWF];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1458,8 +1472,8 @@ __global__ __launch_bounds__(4 * WAVE) void wino2_vtransform_kernel(
   const int kc = lane >> 4, tx = lane & 7, ty = 2 * wm + ((lane >> 3) & 1);
   const int roff = kc * kChF + 4 * ty * kRowF + 4 * tx;
   float a[18];
-  if (HH == 0) w2::W2_TRANSFORM<0, kRowF>(R + roff, a);
-  else w2::W2_TRANSFORM<1, kRowF>(R + roff, a);
+  if (HH == 0) w2::half_transform_pk<0, kRowF>(R + roff, a);
+  else w2::half_transform_pk<1, kRowF>(R + roff, a);
   // the lane's a[18] as wave stores of 1 KB (four) and 512 B (one) into the wave's [chunk][lane] part
   float* o = V + (size_t)blockIdx.x * w2::kVF + wv * w2::kVWF;
 #pragma unroll
@@ -1471,20 +1485,18 @@ __global__ __launch_bounds__(4 * WAVE) void wino2_vtransform_kernel(
 }  // namespace
 
 extern "C" int skp_wino2_weights(const float* w, int K, int C, int flip, float* U, void* stream) {
-  SKP_CHECK_ARG(w && U, "null pointer");
-  SKP_CHECK_ARG(K > 0 && C > 0, "non-positive shape");
-  SKP_CHECK_ARG(K % w2::kNC == 0, "output channels must be a multiple of 32");
+  const char* err = weights_args_error(w, U, K, C);
+  SKP_CHECK_ARG(!err, err);
   const long long n = (long long)K * C;
-  hipLaunchKernelGGL(wino2_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), w, K, C,
-                     flip, U);
+  hipLaunchKernelGGL(wino_weights_kernel<w2::kUP>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), w,
+                     K, C, flip, U);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }
 
 extern "C" int skp_wino2s2_weights(const float* w, int K, int C, float* U, void* stream) {
-  SKP_CHECK_ARG(w && U, "null pointer");
-  SKP_CHECK_ARG(K > 0 && C > 0, "non-positive shape");
-  SKP_CHECK_ARG(K % w2::kNC == 0, "output channels must be a multiple of 32");
+  const char* err = weights_args_error(w, U, K, C);
+  SKP_CHECK_ARG(!err, err);
   const long long n = (long long)K * C;
   hipLaunchKernelGGL(wino2s2_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), w, K,
                      C, U);
@@ -1492,104 +1504,65 @@ extern "C" int skp_wino2s2_weights(const float* w, int K, int C, float* U, void*
   return SKP_OK;
 }
 
+namespace {
+// The launch of the three region-staged forms, which take the same kernel arguments: half-height
+// blocks of 32 × 16 pixels (or nblk pairs of 16×16 images) × K/32 channel blocks × nsplit.
+// kernel_of(E) → the form's kernel with epilogue E; hw = pixels per output plane.
+// Tile-major grid order (kb_major 0: the K/32 channel blocks of one pixel block are consecutive
+// logical workgroups of one XCD, sharing its input region — or its V slab, fetched from HBM once —
+// in L2) measured 1-2% ahead of channel-block-major at every VAE / UNet shape, U size regardless.
+using W2Kernel = void (*)(const float*, const float*, const float*, const float*, float*, int, int, int, int, int, int,
+                          int, int, int, int, int, int, float2*);
+template <int NEPI, class KernelOf>
+int wino2_launch(const char* entry, KernelOf&& kernel_of, const float* x, const float* U, const float* bias,
+                 const float* residual, float* y, int B, int C, int K, int H, int W, long long nblk, int hw, int nsplit,
+                 float* ws, float* gn_part, void* stream) {
+  const int bw = W / 32, bpi = (H / 16) * bw, nkb = K / w2::kNC;
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((unsigned)(nblk * nkb * nsplit));
+  return conv_launch(entry, bias, residual, y, ws, nsplit, B, K, hw, SKP_WINO2_DEBUG, true, st,
+                     [&](int epi, float* out, int flags) {
+                       const W2Kernel kernel = with_epi<NEPI>(epi, kernel_of);
+                       hipLaunchKernelGGL(kernel, grid, dim3(w2::kNW * WAVE), 0, st, x, U, bias, residual, out, B, C, K, H,
+                                          W, bw, bpi, (int)nblk, nkb, 0, C / nsplit, flags,
+                                          reinterpret_cast<float2*>(gn_part));
+                     });
+}
+}  // namespace
+
 // The VAE's Downsample2D (diffusers: F.pad(x, (0, 1, 0, 1)) then a 3×3 stride-2 convolution; reference
 // ptp_utils.py:289-304 encodes through it): y[oy, ox] taps rows 2oy..2oy+2 and columns 2ox..2ox+2 with a
 // zero row / column past the bottom-right edge.  The S2 form of wino2_body computes it as 2×2 output tiles of
 // 25 products (U from skp_wino2s2_weights) on the stride-1 kernel's staged regions, whose out-of-range row /
 // column is that zero pad, with the bias in its epilogue: no padded copy, no NCHW↔NHWC transposes, no bias pass.
-namespace {
-// flag 128 of the kernels' flag word: non-temporal output stores, for outputs of at least 256 MB
-// (larger than the Infinity Cache: the next layer re-reads them from HBM either way, and the stream
-// then does not evict the input regions / weights the other workgroups re-read from L2)
-int wino_nt_flag(long long out_bytes, int nsplit) {
-  if (nsplit > 1) return 0;   // split-K partials are re-read by the reduction
-  return out_bytes >= (256LL << 20) ? 128 : 0;
-}
-}  // namespace
-
 extern "C" int skp_conv3x3s2_f2(const float* x, const float* U, const float* bias, float* y, int B, int C, int K,
                                 int H, int W, int nsplit, float* ws, void* stream) {
-  SKP_CHECK_ARG(x && U && y, "null pointer");
-  SKP_CHECK_ARG(B > 0 && C > 0 && K > 0 && H > 0 && W > 0, "non-positive shape");
-  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
-  SKP_CHECK_ARG(K % w2::kNC == 0, "output channels must be a multiple of 32");
-  SKP_CHECK_ARG(H % 32 == 0 && W % 32 == 0, "H and W must be multiples of 32");
-  SKP_CHECK_ARG(nsplit >= 1 && C % (w2::kCK * nsplit) == 0, "nsplit must divide C into multiples of 4");
-  SKP_CHECK_ARG(nsplit == 1 || ws, "split-K needs a workspace of nsplit·B·K·(H/2)·(W/2) floats");
-  SKP_CHECK_ARG(aligned16(x) && aligned16(U) && aligned16(y) && (!ws || aligned16(ws)), "tensors must be 16-byte aligned");
-  SKP_CHECK_ARG((long long)B * C * H * W * 4 < 0x7fffffffLL, "input larger than 2 GiB (32-bit buffer offsets)");
-  const int bw = W / 32, bpi = (H / 16) * bw;
-  const long long nblk = (long long)B * bpi;
-  const int nkb = K / w2::kNC;
-  SKP_CHECK_ARG(nblk * nkb * nsplit <= 0x7fffffffLL, "grid too large");
-  float* out = nsplit > 1 ? ws : y;
-  hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)(nblk * nkb * nsplit));
-  const int fl = SKP_WINO2_DEBUG | wino_nt_flag((long long)B * K * (H / 2) * (W / 2) * 4, nsplit);
-  if (nsplit == 1 && bias)
-    hipLaunchKernelGGL((wino2_kernel<1, 8, 4, true>), grid, dim3(4 * WAVE), 0, st, x, U, bias, nullptr, out, B, C, K, H,
-                       W, bw, bpi, (int)nblk, nkb, 0, C / nsplit, fl, nullptr);
-  else
-    hipLaunchKernelGGL((wino2_kernel<0, 8, 4, true>), grid, dim3(4 * WAVE), 0, st, x, U, nullptr, nullptr, out, B, C, K,
-                       H, W, bw, bpi, (int)nblk, nkb, 0, C / nsplit, fl, nullptr);
-  SKP_LAUNCH_CHECK();
-  if (nsplit > 1) return splitk_reduce(ws, nsplit, B, K, (H / 2) * (W / 2), bias, nullptr, y, st);
-  return SKP_OK;
+  const ConvArgs a{x && U && y, all_aligned16({x, U, y, ws}), ws, nullptr, B, C, K, H, W, nsplit, 1};
+  const char* err = conv_args_error(kHW32 | kStride2 | kOffsets32, a);
+  const long long nblk = (long long)B * (H / 16) * (W / 32);
+  if (!err && nblk * (K / w2::kNC) * nsplit > kMaxGrid) err = "grid too large";
+  SKP_CHECK_ARG(!err, err);
+  return wino2_launch<2>(
+      __func__, [](auto E) -> W2Kernel { return wino2_kernel<E(), 8, true>; }, x, U, bias, nullptr, y, B, C, K, H, W, nblk,
+      (H / 2) * (W / 2), nsplit, ws, nullptr, stream);
 }
 
 extern "C" int skp_conv3x3_wino2_gn(const float* x, const float* U, const float* bias, const float* residual, float* y,
                                     int B, int C, int K, int H, int W, int nsplit, float* ws, float* gn_part,
                                     void* stream) {
-  SKP_CHECK_ARG(x && U && y, "null pointer");
-  SKP_CHECK_ARG(!gn_part || (nsplit == 1 && H % 32 == 0 && W % 32 == 0 && (reinterpret_cast<uintptr_t>(gn_part) & 7) == 0),
-                "gn_part: one split, H and W multiples of 32, 8-byte aligned");
-  SKP_CHECK_ARG(B > 0 && C > 0 && K > 0 && H > 0 && W > 0, "non-positive shape");
-  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
-  SKP_CHECK_ARG(K % w2::kNC == 0, "output channels must be a multiple of 32");
-  const bool g16 = H == 16 && W == 16;
-  SKP_CHECK_ARG((H % 32 == 0 && W % 32 == 0) || (g16 && B % 4 == 0),
-                "H and W must be multiples of 32, or 16×16 with B a multiple of 4");
-  SKP_CHECK_ARG(nsplit >= 1 && C % (w2::kCK * nsplit) == 0, "nsplit must divide C into multiples of 4");
-  SKP_CHECK_ARG(nsplit == 1 || ws, "split-K needs a workspace of nsplit·B·K·H·W floats");
-  SKP_CHECK_ARG(aligned16(x) && aligned16(U) && aligned16(y) && (!residual || aligned16(residual)) &&
-                    (!ws || aligned16(ws)),
-                "tensors must be 16-byte aligned");
-  SKP_CHECK_ARG((long long)B * C * H * W * 4 < 0x7fffffffLL, "input larger than 2 GiB (32-bit buffer offsets)");
+  const ConvArgs a{x && U && y, all_aligned16({x, U, y, residual, ws}), ws, gn_part, B, C, K, H, W, nsplit, 1};
+  const char* err = conv_args_error(kHW32 | kOr16x16 | kOffsets32, a);
   // half-height blocks (32 × 16 pixels, 4 waves, two workgroups per CU: one's prologue / epilogue
-  // overlaps the other's stage loop), 5-11% faster than the 32 × 32 one-workgroup-per-CU form at
-  // every VAE / UNet shape (profiles/r03al_wino_half_ab.txt); the 16×16 geometry as two images per
+  // overlaps the other's stage loop), 5-11% faster than the 32 × 32 one-workgroup-per-CU form (since
+  // removed) at every VAE / UNet shape (profiles/r03al_wino_half_ab.txt); the 16×16 geometry as two images per
   // 4-wave workgroup, two workgroups per CU (profiles/r03ap_wino_half16_ab.txt)
-  const int bw = W / 32, bpi = (H / 16) * bw;
-  const long long nblk = g16 ? B / 2 : (long long)B * bpi;
-  const int nkb = K / w2::kNC;
-  SKP_CHECK_ARG(nblk * nkb * nsplit <= 0x7fffffffLL, "grid too large");
-  const int dbg = SKP_WINO2_DEBUG;
-  // tile-major (the channel blocks of one pixel block back to back, sharing its input region in
-  // L2) measured 1-2% ahead of channel-block-major at every VAE / UNet shape, U size regardless
-  const int kb_major = 0;
-  const int epi = nsplit > 1 ? 0 : (bias ? 1 : 0) | (residual ? 2 : 0);
-  float* out = nsplit > 1 ? ws : y;
-  hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)(nblk * nkb * nsplit));
-  const int fl = dbg | wino_nt_flag((long long)B * K * H * W * 4, nsplit);
-  float2* gnp = reinterpret_cast<float2*>(gn_part);
-#define SKP_WG2(E)                                                                                            \
-  if (g16)                                                                                                    \
-    hipLaunchKernelGGL((wino2_kernel<E, 4, 4>), grid, dim3(4 * WAVE), 0, st, x, U, bias, residual, out, B, C, K,  \
-                       H, W, bw, bpi, (int)nblk, nkb, kb_major, C / nsplit, fl, nullptr);                              \
-  else                                                                                                        \
-    hipLaunchKernelGGL((wino2_kernel<E, 8, 4>), grid, dim3(4 * WAVE), 0, st, x, U, bias, residual, out, B, C, K,  \
-                       H, W, bw, bpi, (int)nblk, nkb, kb_major, C / nsplit, fl, gnp)
-  switch (epi) {
-    case 0: SKP_WG2(0); break;
-    case 1: SKP_WG2(1); break;
-    case 2: SKP_WG2(2); break;
-    default: SKP_WG2(3); break;
-  }
-#undef SKP_WG2
-  SKP_LAUNCH_CHECK();
-  if (nsplit > 1) return splitk_reduce(ws, nsplit, B, K, H * W, bias, residual, y, st);
-  return SKP_OK;
+  const bool g16 = H == 16 && W == 16;
+  const long long nblk = g16 ? B / 2 : (long long)B * (H / 16) * (W / 32);
+  if (!err && nblk * (K / w2::kNC) * nsplit > kMaxGrid) err = "grid too large";
+  SKP_CHECK_ARG(!err, err);
+  return wino2_launch<4>(
+      __func__, [g16](auto E) -> W2Kernel { return g16 ? wino2_kernel<E(), 4> : wino2_kernel<E(), 8>; }, x, U, bias,
+      residual, y, B, C, K, H, W, nblk, H * W, nsplit, ws, gn_part, stream);
 }
 
 extern "C" int skp_conv3x3_wino2(const float* x, const float* U, const float* bias, const float* residual, float* y,
@@ -1613,7 +1586,7 @@ int vtransform_launch(const float* x, const float* stats, const float* gamma, co
                       int G, int act, float* V, int B, int C, int H, int W, void* stream) {
   const int bw = W / 32, bpi = (H / 16) * bw;
   const long long nwg = (long long)B * bpi * (C / w2::kCK);
-  if (nwg > 0x7fffffffLL) return -2;
+  if (nwg > kMaxGrid) return -2;
   const dim3 grid((unsigned)nwg), block(4 * WAVE);
   hipStream_t st = as_stream(stream);
   if (!stats) hipLaunchKernelGGL(wino2_vtransform_kernel<0>, grid, block, 0, st, x, stats, gamma, beta, shift, G, V, C, H, W, bw, bpi);
@@ -1624,13 +1597,11 @@ int vtransform_launch(const float* x, const float* stats, const float* gamma, co
 }  // namespace
 
 extern "C" int skp_wino2_vtransform(const float* x, float* V, int B, int C, int H, int W, void* stream) {
-  SKP_CHECK_ARG(x && V, "null pointer");
-  SKP_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "non-positive shape");
-  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
-  SKP_CHECK_ARG(H % 32 == 0 && W % 32 == 0, "H and W must be multiples of 32");
-  SKP_CHECK_ARG(aligned16(x) && aligned16(V), "tensors must be 16-byte aligned");
-  SKP_CHECK_ARG(vtransform_launch(x, nullptr, nullptr, nullptr, nullptr, 0, 0, V, B, C, H, W, stream) == 0,
-                "grid too large");
+  const ConvArgs a{x && V, all_aligned16({x, V}), nullptr, nullptr, B, C, w2::kNC, H, W, 1, 1};
+  const char* err = conv_args_error(kHW32, a);
+  if (!err && vtransform_launch(x, nullptr, nullptr, nullptr, nullptr, 0, 0, V, B, C, H, W, stream) != 0)
+    err = "grid too large";
+  SKP_CHECK_ARG(!err, err);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }
@@ -1638,13 +1609,11 @@ extern "C" int skp_wino2_vtransform(const float* x, float* V, int B, int C, int 
 extern "C" int skp_wino2_vtransform_gn(const float* x, const float* stats, const float* gamma, const float* beta,
                                        const float* shift, int G, int act, float* V, int B, int C, int H, int W,
                                        void* stream) {
-  SKP_CHECK_ARG(x && V && stats && gamma && beta, "null pointer");
-  SKP_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "non-positive shape");
-  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
-  SKP_CHECK_ARG(G > 0 && C % G == 0, "C must be divisible by G");
-  SKP_CHECK_ARG(H % 32 == 0 && W % 32 == 0, "H and W must be multiples of 32");
-  SKP_CHECK_ARG(aligned16(x) && aligned16(V), "tensors must be 16-byte aligned");
-  SKP_CHECK_ARG(vtransform_launch(x, stats, gamma, beta, shift, G, act, V, B, C, H, W, stream) == 0, "grid too large");
+  const ConvArgs a{x && V && stats && gamma && beta, all_aligned16({x, V}), nullptr, nullptr, B, C, w2::kNC, H, W, 1, G};
+  const char* err = conv_args_error(kHW32, a);
+  if (!err && vtransform_launch(x, stats, gamma, beta, shift, G, act, V, B, C, H, W, stream) != 0)
+    err = "grid too large";
+  SKP_CHECK_ARG(!err, err);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }
@@ -1652,44 +1621,14 @@ extern "C" int skp_wino2_vtransform_gn(const float* x, const float* stats, const
 extern "C" int skp_conv3x3_wino2_v_gn(const float* V, const float* U, const float* bias, const float* residual,
                                       float* y, int B, int C, int K, int H, int W, int nsplit, float* ws,
                                       float* gn_part, void* stream) {
-  SKP_CHECK_ARG(V && U && y, "null pointer");
-  SKP_CHECK_ARG(!gn_part || (nsplit == 1 && (reinterpret_cast<uintptr_t>(gn_part) & 7) == 0),
-                "gn_part: one split, 8-byte aligned");
-  SKP_CHECK_ARG(B > 0 && C > 0 && K > 0 && H > 0 && W > 0, "non-positive shape");
-  SKP_CHECK_ARG(C % w2::kCK == 0, "input channels must be a multiple of 4");
-  SKP_CHECK_ARG(K % w2::kNC == 0, "output channels must be a multiple of 32");
-  SKP_CHECK_ARG(H % 32 == 0 && W % 32 == 0, "H and W must be multiples of 32");
-  SKP_CHECK_ARG(nsplit >= 1 && C % (w2::kCK * nsplit) == 0, "nsplit must divide C into multiples of 4");
-  SKP_CHECK_ARG(nsplit == 1 || ws, "split-K needs a workspace of nsplit·B·K·H·W floats");
-  SKP_CHECK_ARG(aligned16(V) && aligned16(U) && aligned16(y) && (!residual || aligned16(residual)) &&
-                    (!ws || aligned16(ws)),
-                "tensors must be 16-byte aligned");
-  const int bw = W / 32, bpi = (H / 16) * bw;
-  const long long nblk = (long long)B * bpi;
-  const int nkb = K / w2::kNC;
-  SKP_CHECK_ARG(nblk * nkb * nsplit <= 0x7fffffffLL, "grid too large");
-  // tile-major: the K/32 channel blocks of one tile block are consecutive logical workgroups of
-  // one XCD, so a V slab is fetched from HBM once and its other K/32 − 1 reads hit that XCD's L2
-  const int kb_major = 0;
-  const int epi = nsplit > 1 ? 0 : (bias ? 1 : 0) | (residual ? 2 : 0);
-  float* out = nsplit > 1 ? ws : y;
-  hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)(nblk * nkb * nsplit));
-  const int fl = SKP_WINO2_DEBUG | wino_nt_flag((long long)B * K * H * W * 4, nsplit);
-  float2* gnp = reinterpret_cast<float2*>(gn_part);
-#define SKP_WV(E)                                                                                                  \
-  hipLaunchKernelGGL((wino2v_kernel<E>), grid, dim3(4 * WAVE), 0, st, V, U, bias, residual, out, B, C, K, H, W, bw, \
-                     bpi, (int)nblk, nkb, kb_major, C / nsplit, fl, gnp)
-  switch (epi) {
-    case 0: SKP_WV(0); break;
-    case 1: SKP_WV(1); break;
-    case 2: SKP_WV(2); break;
-    default: SKP_WV(3); break;
-  }
-#undef SKP_WV
-  SKP_LAUNCH_CHECK();
-  if (nsplit > 1) return splitk_reduce(ws, nsplit, B, K, H * W, bias, residual, y, st);
-  return SKP_OK;
+  const ConvArgs a{V && U && y, all_aligned16({V, U, y, residual, ws}), ws, gn_part, B, C, K, H, W, nsplit, 1};
+  const char* err = conv_args_error(kHW32, a);
+  const long long nblk = (long long)B * (H / 16) * (W / 32);
+  if (!err && nblk * (K / w2::kNC) * nsplit > kMaxGrid) err = "grid too large";
+  SKP_CHECK_ARG(!err, err);
+  return wino2_launch<4>(
+      __func__, [](auto E) -> W2Kernel { return wino2v_kernel<E()>; }, V, U, bias, residual, y, B, C, K, H, W, nblk, H * W,
+      nsplit, ws, gn_part, stream);
 }
 
 extern "C" int skp_conv3x3_wino2_v(const float* V, const float* U, const float* bias, const float* residual, float* y,

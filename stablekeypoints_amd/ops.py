@@ -1581,11 +1581,11 @@ def tokens_proj_out(h, weight, bias, residual):
 
 
 # --------------------------------------------------------------------------- 3×3 convolution
-# Transformed weights per frozen weight tensor: {weight: {flip: (version, U)}} (U = G g Gᵀ,
-# K·C·36 floats; built once, on first use, on the weight's device and stream).
+# Transformed weights per frozen weight tensor (U = G g Gᵀ; built once per form, on first use, on
+# the weight's device and stream).
 import weakref as _weakref
 
-_WINO_U = {}   # id(weight) -> (weakref(weight), {(flip, v2): (version, U)})
+_WINO_U = {}   # id(weight) -> (weakref(weight), {(flip, form): (version, U)})
 # Shapes whose grid stays below this even after splitting go to MIOpen.
 WINO_MIN_WORKGROUPS = 128
 # Which kernel takes an eligible shape: "auto" = skp_conv3x3_wino2 where H and W are multiples
@@ -1605,36 +1605,52 @@ def _wino_v2(H, W, B=None):
     return (H % 32 == 0 and W % 32 == 0) or (H == 16 and W == 16 and B is not None and B % 4 == 0)
 
 
-def _wino_u(weight, flip, v2=False):
-    ent = _WINO_U.get(id(weight))
+def _wino_u_cached(weight, flip, form, build):
+    """The (flip, form) entry of ``weight``'s transformed weights, ``build()`` on first use and again
+    after an in-place change of the weight (``_version``); the weight's entries leave with it."""
+    key = id(weight)
+    ent = _WINO_U.get(key)
     if ent is None or ent[0]() is not weight:
-        key = id(weight)
-        ent = (_weakref.ref(weight, lambda _r, key=key: _WINO_U.pop(key, None)), {})
-        _WINO_U[key] = ent
-    per = ent[1]
-    hit = per.get((flip, v2))
-    if hit is not None and hit[0] == weight._version:
-        return hit[1]
-    w = _c(weight.detach())
-    K, C = (w.shape[0], w.shape[1]) if not flip else (w.shape[1], w.shape[0])
-    if v2 == "s2":   # the stride-2 form's 25 positions in rows of 28 (skp_wino2s2_weights; never flipped)
-        U = torch.empty(K * C * 28, device=w.device, dtype=F32)
-        call("skp_wino2s2_weights", ptr(w), K, C, ptr(U), stream(w.device))
-    else:
-        U = torch.empty(K * C * (40 if v2 else 36), device=w.device, dtype=F32)
-        call("skp_wino2_weights" if v2 else "skp_wino_weights", ptr(w), K, C, int(flip), ptr(U), stream(w.device))
-    per[(flip, v2)] = (weight._version, U)
-    return U
+        ent = _WINO_U[key] = (_weakref.ref(weight, lambda _r: _WINO_U.pop(key, None)), {})
+    hit = ent[1].get((flip, form))
+    if hit is None or hit[0] != weight._version:
+        hit = ent[1][(flip, form)] = (weight._version, build())
+    return hit[1]
+
+
+def _wino_u(weight, flip, v2=False):
+    def build():
+        w = _c(weight.detach())
+        K, C = (w.shape[0], w.shape[1]) if not flip else (w.shape[1], w.shape[0])
+        if v2 == "s2":   # the stride-2 form's 25 positions in rows of 28 (skp_wino2s2_weights; never flipped)
+            U = torch.empty(K * C * 28, device=w.device, dtype=F32)
+            call("skp_wino2s2_weights", ptr(w), K, C, ptr(U), stream(w.device))
+        else:
+            U = torch.empty(K * C * (40 if v2 else 36), device=w.device, dtype=F32)
+            call("skp_wino2_weights" if v2 else "skp_wino_weights", ptr(w), K, C, int(flip), ptr(U), stream(w.device))
+        return U
+    return _wino_u_cached(weight, flip, v2, build)
+
+
+def _batch_chunks(B, per_img_bytes):
+    """(b0, b1) ranges of a batch whose inputs each stay below 2 GiB: the kernels address x through
+    32-bit buffer offsets."""
+    bmax = max(1, (2 ** 31 - 1) // per_img_bytes)
+    for b0 in range(0, B, bmax):
+        yield b0, min(B, b0 + bmax)
 
 
 def _wino_plan_uncached(B, C, K, H, W, force):
     """(v2, nsplit, workgroups) for a (B, C, H, W) → (B, K, H, W) convolution.
 
-    One workgroup per CU (their LDS), so a grid runs in ceil(workgroups / 256) rounds of
-    (stages × ≈2.4 µs + ≈5 µs); splitting the input channels S ways shortens a workgroup S-fold
-    and adds (S + 1) passes over the output for the partial sums.  The split with the least
-    modelled time wins (measured at batch 8: 64² × 320 and 32² × 640 channels at 4 and 8 splits
-    instead of 1.25 and 0.63 rounds)."""
+    Splitting the input channels S ways shortens a workgroup S-fold and adds (S + 1) passes over the
+    output for the partial sums; the split with the least modelled time wins (measured at batch 8:
+    64² × 320 and 32² × 640 channels at 4 and 8 splits instead of 1.25 and 0.63 rounds).
+    skp_conv3x3_wino2 (v2; the V-staged and stride-2 forms are planned as it): 2·wgs half-height
+    workgroups, two co-resident per CU; a CU holding k of them runs ⌊k/2⌋ pairs at ≈1.72 µs per stage
+    and a lone one at ≈1.48, the partial sums move at ≈2 TB/s (profiles/r03am_split_sweep.txt).
+    skp_conv3x3_wino: one workgroup per CU (its LDS), ⌈workgroups / 256⌉ rounds of
+    (stages × ≈2.4 µs + ≈5 µs); the partial sums move at ≈5 TB/s."""
     v2 = _wino_v2(H, W, B)
     if v2:
         wgs = (B // 4 if H == 16 else B * (H // 32) * (W // 32)) * (K // 32)
@@ -1643,13 +1659,9 @@ def _wino_plan_uncached(B, C, K, H, W, force):
     else:
         wgs = -(-(B * (H // 4) * (W // 4)) // 64) * (K // 32)
     out_bytes = B * K * H * W * 4
-    half = v2   # libskp's half-height blocks: two co-resident workgroups per CU
 
     def cost(s):
-        if half:
-            # half-height blocks (2·wgs workgroups, two co-resident per CU): a CU holding k of them
-            # runs ⌊k/2⌋ pairs at ≈1.72 µs per stage and a lone one at ≈1.48; the partial sums
-            # cost (s + 1) passes at ≈2 TB/s (fitted to the split sweep, profiles/r03am_split_sweep.txt)
+        if v2:
             k = -(-2 * wgs * s // 256)
             st = C // s // 4
             return (k // 2) * st * 1.72e-6 + (k % 2) * st * 1.48e-6 + (s > 1) * (s + 1) * out_bytes / 2e12
@@ -1693,7 +1705,7 @@ def wino_eligible(B, C, K, H, W, min_workgroups=None):
 # WINO_GEMM_MAX_HW = the largest H·W that takes it (tests set 0 to cover the fused kernels).
 WINO_GEMM_MAX_HW = 1024
 WINO_GEMM_MIN_CH = 256
-# G of F(4×4, 3×3) at the points (0, 1, −1, 1/2, −2, ∞) (skp_conv.hip wino_weights_kernel's Gm)
+# G of F(4×4, 3×3) at the points (0, 1, −1, 1/2, −2, ∞) (skp_conv.hip's kG)
 _WINO_G = ((1.0, 0.0, 0.0), (1 / 3, 1 / 3, 1 / 3), (-1 / 3, 1 / 3, -1 / 3), (-16 / 15, -8 / 15, -4 / 15),
            (1 / 15, -2 / 15, 4 / 15), (0.0, 0.0, 1.0))
 
@@ -1707,28 +1719,18 @@ def _wino_u_gemm(weight, flip):
     """U[p = 6i + j] (36, C, K) = (G g Gᵀ)[i][j] in fp64 → fp32, g = w[k][c] (flip 0) or
     rot180(w[c][k]) (flip 1, the input-gradient convolution); cached per frozen weight like
     _wino_u."""
-    ent = _WINO_U.get(id(weight))
-    if ent is None or ent[0]() is not weight:
-        key = id(weight)
-        ent = (_weakref.ref(weight, lambda _r, key=key: _WINO_U.pop(key, None)), {})
-        _WINO_U[key] = ent
-    hit = ent[1].get((flip, "gemm"))
-    if hit is not None and hit[0] == weight._version:
-        return hit[1]
-    w = weight.detach().double()
-    g = w.flip(2, 3).transpose(0, 1) if flip else w                 # (K, C, 3, 3) of this convolution
-    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
-    U = torch.einsum("iu,kcuv,jv->ijck", G, g, G).reshape(36, g.shape[1], g.shape[0]).float().contiguous()
-    ent[1][(flip, "gemm")] = (weight._version, U)
-    return U
+    def build():
+        w = weight.detach().double()
+        g = w.flip(2, 3).transpose(0, 1) if flip else w                 # (K, C, 3, 3) of this convolution
+        G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
+        return torch.einsum("iu,kcuv,jv->ijck", G, g, G).reshape(36, g.shape[1], g.shape[0]).float().contiguous()
+    return _wino_u_cached(weight, flip, "gemm", build)
 
 
 # The product as (36, K, T), so the output transform reads it and writes the tiles coalesced (and
 # leaves the next GroupNorm's statistics partials, as the fused kernel does); r04 measured it ahead
 # of the (36, T, K) product with per-lane scattered tile stores (skp_wino_out_transform, kept in
 # the ABI).
-
-
 def _wino_gemm_conv(x, weight, flip, bias, residual, K, gn=False):
     B, C, H, W = x.shape
     T = B * (H // 4) * (W // 4)
@@ -1756,16 +1758,13 @@ def _wino_conv(x, weight, flip, bias, residual, K, gn=False):
     if _wino_gemm_ok(B, C, K, H, W):
         return _wino_gemm_conv(x, weight, flip, bias, residual, K, gn)
     y = torch.empty(B, K, H, W, device=x.device, dtype=F32)
-    # the kernels address x through 32-bit buffer offsets: batches above 2 GiB run in chunks
-    per_img = C * H * W * 4
-    bmax = max(1, (2 ** 31 - 1) // per_img)
+    chunks = list(_batch_chunks(B, C * H * W * 4))
     gnp = None
     if gn and GN_EPI and H % 32 == 0 and W % 32 == 0 and all(
-            _wino_plan(min(B, b0 + bmax) - b0, C, K, H, W)[:2] == (True, 1) for b0 in range(0, B, bmax)):
+            _wino_plan(b1 - b0, C, K, H, W)[:2] == (True, 1) for b0, b1 in chunks):
         nseg = (H // 16) * (W // 32)
         gnp = torch.empty(B, K, nseg, 2, device=x.device, dtype=F32)
-    for b0 in range(0, B, bmax):
-        b1 = min(B, b0 + bmax)
+    for b0, b1 in chunks:
         _wino_launch(x[b0:b1], weight, flip, bias, None if residual is None else residual[b0:b1], y[b0:b1], K,
                      None if gnp is None else gnp[b0:b1])
     if gnp is not None:
@@ -1896,9 +1895,7 @@ def conv3x3_s2(x, weight, bias=None):
     y = torch.empty(B, K, H // 2, W // 2, device=x.device, dtype=F32)
     U = _wino_u(weight, False, "s2")
     b = None if bias is None else _c(bias.detach())
-    bmax = max(1, (2 ** 31 - 1) // (C * H * W * 4))   # 32-bit buffer offsets into x
-    for b0 in range(0, B, bmax):
-        b1 = min(B, b0 + bmax)
+    for b0, b1 in _batch_chunks(B, C * H * W * 4):
         _, nsplit, _ = _wino_plan(b1 - b0, C, K, H, W)
         ws = torch.empty(nsplit, b1 - b0, K, H // 2, W // 2, device=x.device, dtype=F32) if nsplit > 1 else None
         with _timed("skp_conv3x3s2_f2", 0):

@@ -91,6 +91,33 @@ def test_conv3x3_vae_shape_and_weight_cache(all_shapes):
     assert _rel(y2, ref2) < 3e-5
 
 
+@pytest.mark.parametrize("form", [False, True, "s2", "gemm"])
+def test_wino_weight_cache_per_form(form):
+    """The transformed-weight cache of every form (_wino_u's three layouts, _wino_u_gemm): a second
+    call returns the same tensor, an in-place weight update a new and different one, and the
+    entry leaves with the weight."""
+    import gc
+    from stablekeypoints_amd import ops
+
+    def transformed(w):
+        return ops._wino_u_gemm(w, False) if form == "gemm" else ops._wino_u(w, False, form)
+
+    g = torch.Generator(device=DEV).manual_seed(5)
+    w = torch.randn(32, 4, 3, 3, device=DEV, generator=g)
+    key = id(w)
+    U = transformed(w)
+    assert transformed(w) is U
+    with torch.no_grad():
+        w.add_(1)
+    U2 = transformed(w)
+    assert U2 is not U and U2.shape == U.shape and not torch.equal(U2, U)
+    assert transformed(w) is U2
+    assert key in ops._WINO_U
+    del w
+    gc.collect()
+    assert key not in ops._WINO_U
+
+
 @pytest.mark.parametrize("H,W", [(32, 32), (64, 96), (16, 16)])
 def test_conv3x3_v2_zero_padding_at_every_edge(all_shapes, H, W):
     """skp_conv3x3_wino2 zero-pads by loading out-of-range rows / 16-B chunks as zeros: a
