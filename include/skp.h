@@ -508,6 +508,27 @@ int skp_tta_reduce_scored_workspace(int B, int n, int S);
 int skp_tta_reduce_scored(const float* maps, int B, int C, int n, int S, const float* theta_inv, float distance,
                           float* pos, float* refined, float* scores, float* avg, void* workspace, void* stream);
 
+/* The k-peak TTA reduce: skp_tta_reduce (eval.py:327-355) then eval.find_k_max_pixels with its
+ * mask_radius (eval.py:62-111) on the average, without the average in memory.
+ *   pos (B, n, num, 2): round j's (row + 0.5, col + 0.5); values (B, n, num): the value that won
+ *   round j, read from the average after j masks; avg (B, n, S, S) optional: the unmasked average,
+ *   skp_tta_reduce's bit for bit.
+ * Equal to skp_tta_reduce(…, avg) followed by skp_k_max_pixels(avg, num, radius2), and to
+ * skp_argmax2d and skp_mask_radius in turn: round 0 is the first-occurrence row-major argmax; before
+ * round j every earlier pick p has multiplied the map by (dx² + dy² > radius2) ? 1.0f : 0.0f,
+ * dx = (float)col − (col_p + 0.5f), dy likewise.  A multiply, not a fill: a masked pixel is 0 and
+ * can still win, +inf · 0 is NaN, NaN wins an argmax and the lowest index wins among NaNs.
+ * Round 0 is skp_tta_reduce's two launches; each later round recomputes only the 64 × 4-pixel tiles
+ * that meet the box around the newest pick (at S = 512 and radius 25.6 at most 28 of 1024) and
+ * merges again: 2 + 2(num − 1) launches, no atomics, deterministic.
+ * workspace: skp_tta_reduce_peaks_workspace(B, n, S, num, radius2) bytes (−1 on a bad shape, num
+ * or radius2), 8-B aligned: skp_tta_reduce's partials and one index per image, token and round.
+ * Rejected before any launch: what skp_tta_reduce rejects, a null values, num outside [1, 16], a
+ * radius2 that is not positive and finite.                                                     */
+int skp_tta_reduce_peaks_workspace(int B, int n, int S, int num, float radius2);
+int skp_tta_reduce_peaks(const float* maps, int B, int C, int n, int S, const float* theta_inv, int num,
+                         float radius2, float* pos, float* values, float* avg, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

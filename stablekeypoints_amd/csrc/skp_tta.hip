@@ -21,6 +21,16 @@
 // launch (one workgroup per image and token) recomputes the average on the box around the peak
 // with the same functions, hence the same bits, for the centroid of eval.py:113-155, the
 // concentration and the coverage.  Three launches, no atomics.
+//
+// The k-peak reduce (skp_tta_reduce_peaks) adds eval.find_k_max_pixels (eval.py:62-111) on that
+// average, again without it in memory: round 0 is the tile kernel and a merge that also leaves the
+// winning index and value; the masks are cumulative, so in round j only the tiles that meet the
+// bounding box of the newest disc (pick j − 1) can change, and a masked-tile kernel recomputes
+// those (average_at: the tile kernel's bits), applies all j masks (the predicate and the multiply
+// of row_argmax_masked, skp_select.hip) and overwrites their partials in place; then the merge
+// again.  2 + 2(num − 1) launches, no atomics.
+#include <algorithm>
+#include <cmath>
 #include <type_traits>
 
 #include "skp_warp.h"
@@ -37,6 +47,7 @@ constexpr int kWaves = kThreads / WAVE;
 constexpr int kTok = 10;
 static_assert(kTok <= 15, "the rest after the kTok passes is split into passes of 8, 4, 2 and 1");
 constexpr int kNoIndex = 0x7fffffff;
+constexpr int kMaxPeaks = 16;   // kMaxSubjects of skp_select.hip
 
 __device__ __forceinline__ bool better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
 
@@ -398,6 +409,104 @@ __global__ __launch_bounds__(kThreads) void tta_window_kernel(const float* __res
   }
 }
 
+// The k-peak merge: tta_merge_kernel's reduction in torch.argmax order (a masked +inf is NaN, and
+// NaN wins; round 0's partials hold none, so there it picks as `better` does), one wave per (image,
+// token).  Leaves round `round`'s position, the value that won it, and its linear index for the
+// next round's masks.
+__global__ __launch_bounds__(WAVE) void tta_merge_peaks_kernel(const float* __restrict__ part_v,
+                                                               const int* __restrict__ part_i, int parts, int S,
+                                                               int num, int round, float* __restrict__ pos,
+                                                               float* __restrict__ values, int* __restrict__ picks) {
+  const size_t o = (size_t)blockIdx.x * parts;
+  float v = -INFINITY;
+  int i = kNoIndex;
+  for (int k = threadIdx.x; k < parts; k += WAVE)
+    if (argmax_better(part_v[o + k], part_i[o + k], v, i)) {
+      v = part_v[o + k];
+      i = part_i[o + k];
+    }
+  wave_argmax(v, i);
+  if (threadIdx.x == 0) {
+    const size_t q = (size_t)blockIdx.x * num + round;
+    pos[2 * q] = (float)(i / S) + 0.5f;
+    pos[2 * q + 1] = (float)(i % S) + 0.5f;
+    values[q] = v;
+    picks[q] = i;
+  }
+}
+
+// Tiles a span of `len` pixels can meet, wherever it starts.
+__host__ __device__ inline int span_tiles(int len, int tile) { return (len + 2 * tile - 2) / tile; }
+
+// Round `round` >= 1 of the k-peak reduce.  grid (B · n · slots): workgroup `slot` of an (image,
+// token) takes the slot-th tile, row-major, of those that meet the box of rows r ± R and columns
+// c ± R around the newest pick (r, c), clipped to the plane; R is such that no pixel outside the box
+// is within the radius (the host picks it), and slots >= the tiles such a box can meet, so slots
+// past the actual count leave at once.  A thread takes the tile kernel's pixel of the tile, forms
+// its average with average_at, multiplies by every pick's mask in pick order and the workgroup
+// overwrites the tile's partial.
+__global__ __launch_bounds__(kThreads) void tta_masked_tile_kernel(const float* __restrict__ maps,
+                                                                   const float* __restrict__ theta_inv, int C, int n,
+                                                                   int S, int num, int round, float radius2, int R,
+                                                                   int slots, const int* __restrict__ picks,
+                                                                   float* __restrict__ part_v,
+                                                                   int* __restrict__ part_i) {
+  __shared__ float s_v[kWaves];
+  __shared__ int s_i[kWaves];
+  const int SS = S * S, bt = blockIdx.x / slots, slot = blockIdx.x % slots;
+  const int b = bt / n, tok = bt % n;
+  const int* pk = picks + (size_t)bt * num;
+  int newest = pk[round - 1];
+  newest = (unsigned)newest < (unsigned)SS ? newest : 0;   // every tile holds a pixel, so it is
+  const int r0 = newest / S, c0 = newest % S;
+  const int ty0 = max(r0 - R, 0) / kTileH, ty1 = min(r0 + R, S - 1) / kTileH;
+  const int tx0 = max(c0 - R, 0) / kTileW, tx1 = min(c0 + R, S - 1) / kTileW;
+  const int ntx = tx1 - tx0 + 1;
+  if (slot >= ntx * (ty1 - ty0 + 1)) return;   // uniform
+  const int ty = ty0 + slot / ntx, tx = tx0 + slot % ntx;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int x = tx * kTileW + wid * 16 + (lane & 15), y = ty * kTileH + (lane >> 4);
+  float v = -INFINITY;
+  int p = kNoIndex;
+  if (x < S && y < S) {
+    float ones;
+    v = average_at(maps + ((size_t)b * C * n + tok) * SS, theta_inv + (size_t)b * C * 6, C, (size_t)n * SS, y, x, S,
+                   ones);
+    p = y * S + x;
+    const float fx = (float)x, fy = (float)y;
+    for (int q = 0; q < round; ++q) {
+      const int pq = pk[q];
+      const float dx = fx - ((float)(pq % S) + 0.5f), dy = fy - ((float)(pq / S) + 0.5f);
+      v = v * ((dx * dx + dy * dy > radius2) ? 1.0f : 0.0f);
+    }
+  }
+  wave_argmax(v, p);
+  if (lane == 0) {
+    s_v[wid] = v;
+    s_i[wid] = p;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 1; k < kWaves; ++k)
+      if (argmax_better(s_v[k], s_i[k], v, p)) {
+        v = s_v[k];
+        p = s_i[k];
+      }
+    const size_t o = (size_t)bt * (tiles_x(S) * tiles_y(S)) + (size_t)ty * tiles_x(S) + tx;
+    part_v[o] = v;
+    part_i[o] = p;
+  }
+}
+
+// The box half-width of a mask: the least R with every pixel more than R rows (or columns) from a
+// pick's outside its disc, (R + 0.5)² > radius2 with room for the float rounding of the predicate;
+// a box wider than the plane is the plane.
+inline int mask_box(float radius2, int S) {
+  const double r = std::sqrt((double)radius2);
+  return r >= (double)S ? S : (int)r + 1;
+}
+
 }  // namespace
 
 extern "C" int skp_tta_reduce_workspace(int B, int n, int S) {
@@ -467,5 +576,53 @@ extern "C" int skp_tta_reduce_scored(const float* maps, int B, int C, int n, int
   hipLaunchKernelGGL(tta_window_kernel, dim3(B * n), dim3(kThreads), 0, st, maps, theta_inv, C, n, S, distance, peak_i,
                      total, refined, scores);
   SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
+// skp_tta_reduce's partials, then one linear index (int) per image, token and round.
+extern "C" int skp_tta_reduce_peaks_workspace(int B, int n, int S, int num, float radius2) {
+  if (num < 1 || num > kMaxPeaks || !(radius2 > 0.0f) || !std::isfinite(radius2)) return -1;
+  const int base = skp_tta_reduce_workspace(B, n, S);
+  if (base <= 0) return -1;
+  const long long bytes = base + (((long long)B * n * num * 4 + 7) & ~7ll);
+  return bytes < (1ll << 31) ? (int)bytes : -1;
+}
+
+extern "C" int skp_tta_reduce_peaks(const float* maps, int B, int C, int n, int S, const float* theta_inv, int num,
+                                    float radius2, float* pos, float* values, float* avg, void* workspace,
+                                    void* stream) {
+  SKP_CHECK_ARG(maps && theta_inv && pos && values && workspace, "null pointer");
+  SKP_CHECK_ARG(B > 0 && C > 0 && n > 0 && S > 0, "non-positive shape");
+  SKP_CHECK_ARG(S >= 2, "S must be at least 2 (the two taps of a row are loaded as a pair)");
+  SKP_CHECK_ARG(S < 46341 && (long long)B * C * n * S * S < (1ll << 31), "maps of 2^31 elements or more");
+  SKP_CHECK_ARG(B <= 65535, "more than 65535 images");
+  SKP_CHECK_ARG(num >= 1 && num <= kMaxPeaks, "num must be in [1, 16]");
+  SKP_CHECK_ARG(radius2 > 0.0f && std::isfinite(radius2), "radius2 must be positive and finite");
+  SKP_CHECK_ARG(skp_tta_reduce_peaks_workspace(B, n, S, num, radius2) > 0, "workspace of 2^31 bytes or more");
+  SKP_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
+  const int tiles = tiles_x(S) * tiles_y(S);
+  const int R = mask_box(radius2, S);
+  const int slots =
+      std::min(span_tiles(2 * R + 1, kTileH), tiles_y(S)) * std::min(span_tiles(2 * R + 1, kTileW), tiles_x(S));
+  SKP_CHECK_ARG(num == 1 || (long long)B * n * slots < (1ll << 31), "masked-tile grid of 2^31 workgroups or more");
+  float* part_v = static_cast<float*>(workspace);
+  int* part_i = reinterpret_cast<int*>(part_v + (size_t)B * n * tiles);
+  int* picks = part_i + (size_t)B * n * tiles;
+  hipStream_t st = as_stream(stream);
+  TileArgs A;
+  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg, A.part_v = part_v, A.part_i = part_i;
+  A.C = C, A.n = n, A.S = S;
+  hipLaunchKernelGGL(tta_tile_kernel<false>, dim3(tiles, B), dim3(kThreads), 0, st, A);
+  SKP_LAUNCH_CHECK();
+  for (int round = 0; round < num; ++round) {
+    if (round) {
+      hipLaunchKernelGGL(tta_masked_tile_kernel, dim3(B * n * slots), dim3(kThreads), 0, st, maps, theta_inv, C, n, S,
+                         num, round, radius2, R, slots, picks, part_v, part_i);
+      SKP_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(tta_merge_peaks_kernel, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, tiles, S, num, round,
+                       pos, values, picks);
+    SKP_LAUNCH_CHECK();
+  }
   return SKP_OK;
 }

@@ -8,7 +8,8 @@ test-time-augmentation average on the same kernels; ``evaluate`` (``:374-539``) 
 keypoints from it and scores them with the reference's five metrics (``keypoint_error``).
 ``predict_keypoints`` (extra) returns the keypoints of a batch of unlabelled images: batched
 captures and the whole TTA reduce (inverse warps, sums, ratio, argmax) in one kernel,
-``skp_tta_reduce``.
+``skp_tta_reduce``; with ``num_subjects`` = k > 1 also the k peaks per token of
+``find_k_max_pixels`` on the average, from ``skp_tta_reduce_peaks``.
 """
 import collections
 import contextlib
@@ -226,13 +227,14 @@ def evaluate(ldm, context, indices, regressor, device="cuda", from_where=("down_
 
 
 KeypointScores = collections.namedtuple("KeypointScores", ["peak", "concentration", "coverage", "refined"])
+KeypointPeaks = collections.namedtuple("KeypointPeaks", ["pos", "value"])
 
 
 @torch.no_grad()
 def predict_keypoints(ldm, images, context, indices, regressor=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
                       noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
                       augmentation_iterations=20, max_loc_strategy="argmax", controllers=None, upscale_size=512,
-                      image_batch=None, return_maps=False, return_scores=False, score_distance=5):
+                      image_batch=None, return_maps=False, return_scores=False, score_distance=5, num_subjects=1):
     """Keypoints of a batch of unlabelled images (extra: the use the reference's demo ends in,
     ``visualize_keypoints``: TTA maps → ``find_max_pixel(map) / 512``, which draws the points and
     does not return them).
@@ -255,14 +257,30 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
     average's peak value, its mass within ``score_distance`` pixels of the peak over its whole mass,
     the share of the copies that saw the peak pixel (each (B, n)), and the
     ``pixel_from_weighted_avg`` centroid around the peak / ``upscale_size`` (B, n, 2); the other
-    outputs are what they are without it.  Single process only: under a process group of more
-    than one rank it raises.
+    outputs are what they are without it.
+
+    With ``num_subjects`` = k > 1 (images that show several instances of the object) each pass is
+    reduced by ``ops.tta_reduce_peaks`` and a ``KeypointPeaks(pos, value)`` comes last: ``pos``
+    (B, n, k, 2) holds per token the k peaks of ``find_k_max_pixels`` on the average (round j is
+    the argmax after the discs of radius 0.05 · ``upscale_size`` around rounds 0 … j − 1 were
+    multiplied by 0) / ``upscale_size``, ``value`` (B, n, k) the value that won each round.  The
+    rounds are per token: round j of one token and round j of another need not belong to the same
+    instance, and grouping the peaks into subjects is left to the caller.  So the first output stays
+    (B, n, 2) (round 0, or the ``weighted_avg`` centroid) and the ``regressor`` is applied to it
+    alone; ``return_maps`` gives the unmasked averages.  ``return_scores`` together with
+    ``num_subjects`` > 1 raises: each needs its own reduce.  Single process only: under a process
+    group of more than one rank it raises.
     """
     from .optimize import _world
     if _world()[0] > 1:
         raise ValueError("predict_keypoints runs in a single process (world size must be 1)")
     if max_loc_strategy not in ("argmax", "weighted_avg"):
         raise ValueError("max_loc_strategy must be 'argmax' or 'weighted_avg'")
+    k = int(num_subjects)
+    if k < 1:
+        raise ValueError("num_subjects must be at least 1")
+    if k > 1 and return_scores:
+        raise ValueError("return_scores and num_subjects > 1 each need their own reduce: ask for one of them")
     imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
     if imgs.dim() == 3:
         imgs = imgs[None]
@@ -280,7 +298,7 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
     per_pass = max(1, int(image_batch))
     weighted = max_loc_strategy == "weighted_avg"
     want_avg = weighted or return_maps
-    pos, avgs, refs, scos = [], [], [], []
+    pos, avgs, refs, scos, pks, vals = [], [], [], [], [], []
     for i0 in range(0, B, per_pass):
         nb = min(per_pass, B - i0)
         aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
@@ -297,6 +315,11 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
                                                      return_avg=want_avg)
             refs.append(ref)
             scos.append(sco)
+        elif k > 1:
+            pk, val, avg = ops.tta_reduce_peaks(maps.reshape(nb, C, n, S, S), th_inv, k, return_avg=want_avg)
+            p = pk[:, :, 0].contiguous()
+            pks.append(pk)
+            vals.append(val)
         else:
             p, avg = ops.tta_reduce(maps.reshape(nb, C, n, S, S), th_inv, return_avg=want_avg)
         del maps, per
@@ -316,4 +339,6 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
     if return_scores:
         sco = torch.cat(scos)
         out.append(KeypointScores(sco[..., 0], sco[..., 1], sco[..., 2], torch.cat(refs) / S))
+    if k > 1:
+        out.append(KeypointPeaks(torch.cat(pks) / S, torch.cat(vals)))
     return out[0] if len(out) == 1 else tuple(out)

@@ -6,7 +6,8 @@ optimize (``optimize_embedding`` → ``embedding.pt``) → find_indices (``find_
 (``all_errors.pt``).  ``--start_from_stage`` resumes from the saved files; ``--start_from_stage predict``
 (extra) instead writes the keypoints of the dataset's images — the stage for unlabelled ``custom``
 folders — from ``embedding.pt`` and ``indices.pt`` (``keypoints.pt``, ``keypoints.csv``, and
-``regressed_keypoints.pt`` when ``regressor.pt`` is there) and stops, in one process.  With ``--visualize``,
+``regressed_keypoints.pt`` when ``regressor.pt`` is there; with ``--num_subjects k`` > 1 also the k peaks per token,
+``subject_keypoints.pt``, ``subject_peak_values.pt`` and ``subject_keypoints.csv``) and stops, in one process.  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -53,7 +54,10 @@ def build_parser():
     p.add_argument("--min_dist", type=float, default=0.1)
     p.add_argument("--furthest_point_num_samples", type=int, default=25)
     p.add_argument("--num_indices", type=int, default=100)
-    p.add_argument("--num_subjects", type=int, default=1)
+    p.add_argument("--num_subjects", type=int, default=1,
+                   help="instances of the object per image: the targets of the optimisation take this many maxima "
+                        "per map, and the predict stage also writes this many peaks per token "
+                        "(subject_keypoints.pt (M, n, k, 2), subject_peak_values.pt (M, n, k), subject_keypoints.csv)")
     p.add_argument("--sharpening_loss_weight", type=float, default=100)
     p.add_argument("--equivariance_attn_loss_weight", type=float, default=1000.0)
     p.add_argument("--layers", type=int, nargs="+", default=[0, 1, 2, 3])
@@ -112,7 +116,12 @@ def predict_stage(args, ldm, controllers, batch=4):
     header: index, file name where the reader has one, the n (row, col) pairs, then the regressed pairs).
     With ``--keypoint_scores`` also ``keypoint_scores.pt`` (M, n, 3) = (peak, concentration, coverage),
     ``refined_keypoints.pt`` (M, n, 2) and ``keypoint_scores.csv`` (no header: index, file name where the
-    reader has one, then per token refined row, refined col, peak, concentration, coverage)."""
+    reader has one, then per token refined row, refined col, peak, concentration, coverage).
+    With ``--num_subjects k`` > 1 also ``subject_keypoints.pt`` (M, n, k, 2), the k peaks per token of
+    ``find_k_max_pixels`` on the TTA average / 512 (round 0 is ``keypoints.pt``'s argmax),
+    ``subject_peak_values.pt`` (M, n, k), the value that won each round, and ``subject_keypoints.csv``
+    (no header: index, file name where the reader has one, then per token and round row, col, value).
+    Round j of two tokens need not belong to the same instance; the regressor sees round 0 only."""
     import csv
     from .datasets import make_dataset
     from .eval import predict_keypoints
@@ -123,7 +132,8 @@ def predict_stage(args, ldm, controllers, batch=4):
     dataset = make_dataset(args.dataset_name, args.dataset_loc, max_len=args.max_len, validation=args.validation,
                            split="test")
     names = _image_names(dataset)
-    kps, regs, scos, refs = [], [], [], []
+    k = int(args.num_subjects)
+    kps, regs, scos, refs, pks, vals = [], [], [], [], [], []
     for i0 in range(0, len(dataset), batch):
         images = torch.stack([dataset[i]["img"] for i in range(i0, min(i0 + batch, len(dataset)))])
         out = predict_keypoints(ldm, images, embedding, indices.cpu(), regressor=regressor, device=args.device,
@@ -132,7 +142,12 @@ def predict_stage(args, ldm, controllers, batch=4):
                                 augment_translate=args.augment_translate,
                                 augmentation_iterations=args.augmentation_iterations,
                                 max_loc_strategy=args.max_loc_strategy, controllers=controllers,
-                                return_scores=args.keypoint_scores)
+                                return_scores=args.keypoint_scores, num_subjects=k)
+        if k > 1:
+            pk = out[-1]
+            out = out[0] if len(out) == 2 else out[:-1]
+            pks.append(pk.pos.cpu())
+            vals.append(pk.value.cpu())
         if args.keypoint_scores:
             sc = out[-1]
             out = out[0] if len(out) == 2 else out[:-1]
@@ -167,12 +182,30 @@ def predict_stage(args, ldm, controllers, batch=4):
                 row = [i] + ([names[i]] if names is not None else [])
                 row += [repr(float(v)) for v in torch.cat([refs[i], scos[i]], dim=-1).reshape(-1)]
                 w.writerow(row)
+    if k > 1:
+        pks = torch.cat(pks) if pks else torch.zeros(0, n, k, 2)
+        vals = torch.cat(vals) if vals else torch.zeros(0, n, k)
+        torch.save(pks, os.path.join(folder, "subject_keypoints.pt"))
+        torch.save(vals, os.path.join(folder, "subject_peak_values.pt"))
+        with open(os.path.join(folder, "subject_keypoints.csv"), "w", newline="") as fh:
+            w = csv.writer(fh)
+            for i in range(pks.shape[0]):
+                row = [i] + ([names[i]] if names is not None else [])
+                row += [repr(float(v)) for v in torch.cat([pks[i], vals[i][..., None]], dim=-1).reshape(-1)]
+                w.writerow(row)
     print(f"predict: {kps.shape[0]} images, {n} keypoints each -> {os.path.join(folder, 'keypoints.pt')}", flush=True)
 
 
 def main(argv=None):
     import numpy as np
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.start_from_stage == "predict":
+        if args.num_subjects < 1:
+            parser.error("--num_subjects must be at least 1")
+        if args.num_subjects > 1 and args.keypoint_scores:
+            parser.error("--start_from_stage predict: --num_subjects > 1 and --keypoint_scores each need their own "
+                         "TTA reduce; run the stage once with each")
     from .launch import launcher_env, spawn_ranks
     # torch.cuda.device_count() does not initialise HIP on this image, so the ranks can still start
     n = ranks_to_start(args, torch.cuda.device_count(), launcher_env())

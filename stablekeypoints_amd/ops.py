@@ -2214,3 +2214,59 @@ def tta_reduce_scored(maps, theta_inv, distance=5, return_avg=False):
         call("skp_tta_reduce_scored", ptr(maps), B, C, n, S, ptr(th), distance, ptr(pos), ptr(refined), ptr(scores),
              ptr(avg), ptr(ws), stream(dev))
     return pos, refined, scores, avg
+
+
+_TTA_PEAKS_WS = {}   # (device, B, n, S, num) -> workspace of skp_tta_reduce_peaks_workspace bytes
+
+
+def tta_reduce_peaks_bytes(B, C, n, S, num, radius=None, avg=False):
+    """Byte model of skp_tta_reduce_peaks: ``tta_reduce_bytes`` plus, for each round after the
+    first, the masked-tile kernel's re-reads: two 8-byte pairs per copy for each pixel of the
+    64 × 4 tiles that the (2(⌊radius⌋ + 1) + 1)² box around a pick can meet."""
+    R = int(0.05 * S if radius is None else radius) + 1
+    span = lambda tile: (2 * R + 2 * tile - 1) // tile
+    tiles = min(span(4), (S + 3) // 4) * min(span(64), (S + 63) // 64)
+    return tta_reduce_bytes(B, C, n, S, avg) + 16 * B * n * C * (num - 1) * tiles * 256
+
+
+def tta_reduce_peaks(maps, theta_inv, num, radius=None, return_avg=False):
+    """``tta_reduce`` with ``num`` peaks per token (skp_tta_reduce_peaks; eval.py:327-355 then :62-111).
+
+    Returns ``(pos, values, avg)``: ``pos`` (B, n, num, 2) holds round j's (row + 0.5, col + 0.5),
+    ``values`` (B, n, num) the value that won round j (read after j masks), ``avg`` the unmasked
+    average (B, n, S, S) when ``return_avg``, else None.  Bit-identical to ``tta_reduce(...,
+    return_avg=True)`` followed by ``find_k_max_pixels`` of the average: round 0 is ``tta_reduce``'s
+    ``pos``, and before round j each earlier pick has multiplied the map by 0 within ``radius`` of
+    itself (``mask_radius``: a masked pixel is 0 and can still win, +inf · 0 is NaN and NaN wins).
+    ``radius=None`` is the reference's 0.05 · S.  ``1 <= num <= 16``.  The average is not in memory
+    unless ``return_avg``.
+    """
+    _lib.require_device(maps, theta_inv)
+    if maps.dim() != 5 or maps.shape[-1] != maps.shape[-2]:
+        raise ValueError(f"tta_reduce_peaks: maps must be (B, C, n, S, S), got {tuple(maps.shape)}")
+    maps = _c(maps)
+    B, C, n, S, _ = maps.shape
+    if tuple(theta_inv.shape) != (B, C, 2, 3):
+        raise ValueError(f"tta_reduce_peaks: theta_inv must be ({B}, {C}, 2, 3), got {tuple(theta_inv.shape)}")
+    num = int(num)
+    if not 1 <= num <= 16:
+        raise ValueError(f"tta_reduce_peaks: num must be in [1, 16], got {num}")
+    radius2 = _radius2(S) if radius is None else float(radius) ** 2
+    if not 0.0 < radius2 < float("inf"):
+        raise ValueError(f"tta_reduce_peaks: radius must be positive and finite, got {radius}")
+    dev = maps.device
+    th = _c(theta_inv.to(dev))
+    key = (dev, B, n, S, num)
+    ws = _TTA_PEAKS_WS.get(key)
+    if ws is None:
+        nbytes = _lib.lib().skp_tta_reduce_peaks_workspace(B, n, S, num, radius2)
+        if nbytes <= 0:
+            raise ValueError(f"tta_reduce_peaks: bad shape B={B}, n={n}, S={S}, num={num}")
+        ws = _TTA_PEAKS_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    pos = torch.empty(B, n, num, 2, device=dev, dtype=F32)
+    values = torch.empty(B, n, num, device=dev, dtype=F32)
+    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
+    with _timed("skp_tta_reduce_peaks", tta_reduce_peaks_bytes(B, C, n, S, num, radius, return_avg)):
+        call("skp_tta_reduce_peaks", ptr(maps), B, C, n, S, ptr(th), num, radius2, ptr(pos), ptr(values), ptr(avg),
+             ptr(ws), stream(dev))
+    return pos, values, avg
