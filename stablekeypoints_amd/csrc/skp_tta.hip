@@ -13,22 +13,28 @@
 //
 // Two launches, no atomics: the tile kernel (one workgroup per image and 64 x 4-pixel piece of a
 // four-row band) leaves one (value, linear index) partial per token and tile; the merge kernel
-// reduces each (image, token)'s partials (the greater value wins, on equal values the lower index).
+// (tta_merge_kernel, the one merge of all three reduces) reduces each (image, token)'s partials
+// (the greater value wins, on equal values the lower index).
 //
 // The scored reduce (skp_tta_reduce_scored) adds, without the average in memory: the tile kernel's
 // scored instantiation leaves the sum of each tile's averaged values beside its partial (double
-// from the lane upward, a fixed tree), the scored merge sums them in a fixed order, and a third
-// launch (one workgroup per image and token) recomputes the average on the box around the peak
-// with the same functions, hence the same bits, for the centroid of eval.py:113-155, the
-// concentration and the coverage.  Three launches, no atomics.
+// from the lane upward, a fixed tree), the merge's kScored instantiation sums them in a fixed order
+// and leaves the peak's value and index, and a third launch (one workgroup per image and token)
+// recomputes the average on the box around the peak with the same functions, hence the same bits,
+// for the centroid of eval.py:113-155, the concentration and the coverage.  Three launches, no
+// atomics.
 //
 // The k-peak reduce (skp_tta_reduce_peaks) adds eval.find_k_max_pixels (eval.py:62-111) on that
-// average, again without it in memory: round 0 is the tile kernel and a merge that also leaves the
-// winning index and value; the masks are cumulative, so in round j only the tiles that meet the
+// average, again without it in memory: round 0 is the tile kernel and the merge, which also leaves
+// the winning index and value; the masks are cumulative, so in round j only the tiles that meet the
 // bounding box of the newest disc (pick j − 1) can change, and a masked-tile kernel recomputes
 // those (average_at: the tile kernel's bits), applies all j masks (the predicate and the multiply
 // of row_argmax_masked, skp_select.hip) and overwrites their partials in place; then the merge
 // again.  2 + 2(num − 1) launches, no atomics.
+//
+// Host side: layout() is the one statement of the workspace (the queries return its size, the entry
+// points take their pointers from its offsets), check_common() the checks the three entry points
+// share, launch_tile() the tile kernel's launch.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -101,6 +107,27 @@ __device__ __forceinline__ double wave_sum_tree(double v) {
 constexpr int kTileW = 64, kTileH = 4;
 __host__ __device__ inline int tiles_x(int S) { return (S + kTileW - 1) / kTileW; }
 __host__ __device__ inline int tiles_y(int S) { return (S + kTileH - 1) / kTileH; }
+// This thread's pixel of tile (tx, ty).
+__device__ __forceinline__ void tile_pixel(int tx, int ty, int& x, int& y) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  x = tx * kTileW + wid * 16 + (lane & 15);
+  y = ty * kTileH + (lane >> 4);
+}
+
+// The plane's pixel of linear index `index` (0 where it is none: the callers' indices come from
+// partials, and every tile holds a pixel, so it is one; the loads around it rely on that) and the
+// box of rows r0 ± R and columns c0 ± R around it, clipped to the plane.
+struct Box {
+  int r0, c0, ylo, yhi, xlo, xhi;
+};
+__device__ __forceinline__ Box clipped_box(int index, int S, int R) {
+  index = (unsigned)index < (unsigned)(S * S) ? index : 0;
+  Box b;
+  b.r0 = index / S, b.c0 = index % S;
+  b.ylo = max(b.r0 - R, 0), b.yhi = min(b.r0 + R, S - 1);
+  b.xlo = max(b.c0 - R, 0), b.xhi = min(b.c0 + R, S - 1);
+  return b;
+}
 
 // A grid record ready for many planes.  The two taps of a row are neighbours in memory, so each
 // row goes as ONE 8-byte load at a column clamped into [0, S − 2] (every load lands inside the
@@ -250,9 +277,8 @@ __global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgsOf<
   __shared__ int s_i[kTok][kWaves];
   __shared__ double s_m[SCORED ? kTok : 1][kWaves];
   const int b = blockIdx.y, tile = blockIdx.x, S = A.S;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int x = (tile % tiles_x(S)) * kTileW + wid * 16 + (lane & 15);
-  const int y = (tile / tiles_x(S)) * kTileH + (lane >> 4);
+  int x, y;
+  tile_pixel(tile % tiles_x(S), tile / tiles_x(S), x, y);
   const bool inside = x < S && y < S;
   const int p = inside ? y * S + x : 0;
   int t0 = 0;
@@ -273,51 +299,48 @@ __global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgsOf<
   if (rest & 1) tile_pass<1, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
 }
 
-// One wave per (image, token): the best of its `parts` partials -> pos (row + 0.5, col + 0.5).
+// The merge of all three reduces, one wave per (image, token): the best of its `parts` partials
+// -> round `round`'s pos (row + 0.5, col + 0.5) at 2·(bt·num + round); plain and scored have num 1
+// and round 0.  The winning value goes to `value` (stride `value_stride`: the scores' first column,
+// or the peaks' values) and its linear index to `index` (the window kernel's peak, or the pick the
+// next round masks) where they are given.  kScored: the mass partials are summed too, in a fixed
+// order (lane k takes partials k, k + 64, … in order, then the wave tree), into `total`.
+//
+// kPeaks reduces in torch.argmax's order (argmax_better: a masked +inf is NaN, and NaN wins), which
+// its rounds after the first need.  Round-0 partials hold no NaN (the tile kernel turns NaN into 0
+// before its argmax), and on NaN-free values argmax_better is `better`: the greater value, on equal
+// values the lower index, a total order, so every variant's round 0 picks the same partial.  The
+// NaN-free reduction stays for kPlain and kScored because it is faster there: measured in their
+// place, the argmax-order merge took 8.3 µs against 6.9 µs (640 waves) and 9.1 against 7.8 (2560).
+enum Variant { kPlain, kScored, kPeaks };
+template <Variant V>
 __global__ __launch_bounds__(WAVE) void tta_merge_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i,
-                                                         int parts, int S, float* __restrict__ pos) {
-  const size_t o = (size_t)blockIdx.x * parts;
-  float v = -INFINITY;
-  int i = kNoIndex;
-  for (int k = threadIdx.x; k < parts; k += WAVE)
-    if (better(part_v[o + k], part_i[o + k], v, i)) {
-      v = part_v[o + k];
-      i = part_i[o + k];
-    }
-  wave_best(v, i);
-  if (threadIdx.x == 0) {
-    pos[2 * (size_t)blockIdx.x] = (float)(i / S) + 0.5f;
-    pos[2 * (size_t)blockIdx.x + 1] = (float)(i % S) + 0.5f;
-  }
-}
-
-// The scored merge: the same reduction of the (value, index) partials, and the mass partials summed
-// in a fixed order (lane k takes partials k, k + 64, … in order, then the wave tree).  Leaves the
-// peak value, its linear index and the total mass for the window kernel.
-__global__ __launch_bounds__(WAVE) void tta_merge_scored_kernel(const float* __restrict__ part_v,
-                                                                const int* __restrict__ part_i,
-                                                                const double* __restrict__ part_m, int parts, int S,
-                                                                float* __restrict__ pos, float* __restrict__ scores,
-                                                                int* __restrict__ peak_i, double* __restrict__ total) {
+                                                         const double* __restrict__ part_m, int parts, int S, int num,
+                                                         int round, float* __restrict__ pos, float* __restrict__ value,
+                                                         int value_stride, int* __restrict__ index,
+                                                         double* __restrict__ total) {
+  constexpr bool MASS = V == kScored, NAN_WINS = V == kPeaks;
   const size_t o = (size_t)blockIdx.x * parts;
   float v = -INFINITY;
   int i = kNoIndex;
   double m = 0.0;
   for (int k = threadIdx.x; k < parts; k += WAVE) {
-    if (better(part_v[o + k], part_i[o + k], v, i)) {
+    if (NAN_WINS ? argmax_better(part_v[o + k], part_i[o + k], v, i) : better(part_v[o + k], part_i[o + k], v, i)) {
       v = part_v[o + k];
       i = part_i[o + k];
     }
-    m += part_m[o + k];
+    if constexpr (MASS) m += part_m[o + k];
   }
-  wave_best(v, i);
-  m = wave_sum_tree(m);
+  if constexpr (NAN_WINS) wave_argmax(v, i);
+  else wave_best(v, i);
+  if constexpr (MASS) m = wave_sum_tree(m);
   if (threadIdx.x == 0) {
-    pos[2 * (size_t)blockIdx.x] = (float)(i / S) + 0.5f;
-    pos[2 * (size_t)blockIdx.x + 1] = (float)(i % S) + 0.5f;
-    scores[3 * (size_t)blockIdx.x] = v;
-    peak_i[blockIdx.x] = i;
-    total[blockIdx.x] = m;
+    const size_t q = (size_t)blockIdx.x * num + round;
+    pos[2 * q] = (float)(i / S) + 0.5f;
+    pos[2 * q + 1] = (float)(i % S) + 0.5f;
+    if (value) value[q * value_stride] = v;
+    if (index) index[q] = i;
+    if constexpr (MASS) total[blockIdx.x] = m;
   }
 }
 
@@ -369,10 +392,8 @@ __global__ __launch_bounds__(kThreads) void tta_window_kernel(const float* __res
   __shared__ double sd[kWaves];
   __shared__ float s_num;
   const int SS = S * S, b = blockIdx.x / n, tok = blockIdx.x % n;
-  int peak = peak_i[blockIdx.x];
-  peak = (unsigned)peak < (unsigned)SS ? peak : 0;   // every tile holds a pixel, so it is; the loads below rely on it
-  const int r0 = peak / S, c0 = peak % S, R = (int)distance;
-  const int ylo = max(r0 - R, 0), yhi = min(r0 + R, S - 1), xlo = max(c0 - R, 0), xhi = min(c0 + R, S - 1);
+  const Box box = clipped_box(peak_i[blockIdx.x], S, (int)distance);
+  const int r0 = box.r0, c0 = box.c0, ylo = box.ylo, yhi = box.yhi, xlo = box.xlo, xhi = box.xhi;
   const int bw = xhi - xlo + 1, cnt = bw * (yhi - ylo + 1);   // <= kMaxBox: distance <= kMaxDistance
   const float* th = theta_inv + (size_t)b * C * 6;
   const float* plane0 = maps + ((size_t)b * C * n + tok) * SS;
@@ -409,32 +430,6 @@ __global__ __launch_bounds__(kThreads) void tta_window_kernel(const float* __res
   }
 }
 
-// The k-peak merge: tta_merge_kernel's reduction in torch.argmax order (a masked +inf is NaN, and
-// NaN wins; round 0's partials hold none, so there it picks as `better` does), one wave per (image,
-// token).  Leaves round `round`'s position, the value that won it, and its linear index for the
-// next round's masks.
-__global__ __launch_bounds__(WAVE) void tta_merge_peaks_kernel(const float* __restrict__ part_v,
-                                                               const int* __restrict__ part_i, int parts, int S,
-                                                               int num, int round, float* __restrict__ pos,
-                                                               float* __restrict__ values, int* __restrict__ picks) {
-  const size_t o = (size_t)blockIdx.x * parts;
-  float v = -INFINITY;
-  int i = kNoIndex;
-  for (int k = threadIdx.x; k < parts; k += WAVE)
-    if (argmax_better(part_v[o + k], part_i[o + k], v, i)) {
-      v = part_v[o + k];
-      i = part_i[o + k];
-    }
-  wave_argmax(v, i);
-  if (threadIdx.x == 0) {
-    const size_t q = (size_t)blockIdx.x * num + round;
-    pos[2 * q] = (float)(i / S) + 0.5f;
-    pos[2 * q + 1] = (float)(i % S) + 0.5f;
-    values[q] = v;
-    picks[q] = i;
-  }
-}
-
 // Tiles a span of `len` pixels can meet, wherever it starts.
 __host__ __device__ inline int span_tiles(int len, int tile) { return (len + 2 * tile - 2) / tile; }
 
@@ -456,16 +451,14 @@ __global__ __launch_bounds__(kThreads) void tta_masked_tile_kernel(const float* 
   const int SS = S * S, bt = blockIdx.x / slots, slot = blockIdx.x % slots;
   const int b = bt / n, tok = bt % n;
   const int* pk = picks + (size_t)bt * num;
-  int newest = pk[round - 1];
-  newest = (unsigned)newest < (unsigned)SS ? newest : 0;   // every tile holds a pixel, so it is
-  const int r0 = newest / S, c0 = newest % S;
-  const int ty0 = max(r0 - R, 0) / kTileH, ty1 = min(r0 + R, S - 1) / kTileH;
-  const int tx0 = max(c0 - R, 0) / kTileW, tx1 = min(c0 + R, S - 1) / kTileW;
+  const Box box = clipped_box(pk[round - 1], S, R);   // around the newest pick
+  const int ty0 = box.ylo / kTileH, ty1 = box.yhi / kTileH, tx0 = box.xlo / kTileW, tx1 = box.xhi / kTileW;
   const int ntx = tx1 - tx0 + 1;
   if (slot >= ntx * (ty1 - ty0 + 1)) return;   // uniform
   const int ty = ty0 + slot / ntx, tx = tx0 + slot % ntx;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int x = tx * kTileW + wid * 16 + (lane & 15), y = ty * kTileH + (lane >> 4);
+  int x, y;
+  tile_pixel(tx, ty, x, y);
   float v = -INFINITY;
   int p = kNoIndex;
   if (x < S && y < S) {
@@ -507,71 +500,110 @@ inline int mask_box(float radius2, int S) {
   return r >= (double)S ? S : (int)r + 1;
 }
 
+// The workspace of every reduce, stated once: the queries return `bytes`, the entry points take
+// their pointers from the offsets.  With T tiles per plane and P = B·n·T partials:
+//   part_v  P floats, part_i  P ints                  (all variants; 8·P bytes)
+//   part_m  P doubles, total  B·n doubles, peak_i  B·n ints in B·n·8 bytes    (scored)
+//   picks   B·n·num ints, rounded up to 8 bytes                               (peaks)
+// `bytes` is −1 for a shape no reduce takes (the queries' answer) and for 2^31 bytes or more.
+struct Layout {
+  long long part_v, part_i, part_m, total, peak_i, picks;   // byte offsets; 0 where the variant has none
+  long long bytes;
+};
+Layout layout(int B, int n, int S, Variant variant, int num) {
+  Layout L = {};
+  L.bytes = -1;
+  if (B <= 0 || n <= 0 || S < 2 || (variant == kPeaks && (num < 1 || num > kMaxPeaks))) return L;
+  const long long bt = (long long)B * n, tiles = (long long)tiles_x(S) * tiles_y(S), big = 1ll << 28;
+  if (bt >= big || tiles >= big || bt * tiles >= big) return L;   // 8·bt·tiles bytes of partials alone
+  const long long parts = bt * tiles;
+  long long end = 0;
+  auto take = [&end](long long nbytes) {
+    const long long at = end;
+    end += nbytes;
+    return at;
+  };
+  L.part_v = take(4 * parts);
+  L.part_i = take(4 * parts);
+  if (variant == kScored) {
+    L.part_m = take(8 * parts);
+    L.total = take(8 * bt);
+    L.peak_i = take(8 * bt);
+  }
+  if (variant == kPeaks) L.picks = take((4 * bt * num + 7) & ~7ll);
+  if (end < (1ll << 31)) L.bytes = end;
+  return L;
+}
+template <class T>
+T* at(void* workspace, long long offset) {
+  return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset);
+}
+
+// The checks the three entry points share, in the order each of them always made them; `own` is
+// the message of the variant's failed checks that come before the workspace's (num and radius2 of
+// the k-peak reduce), or null.  Returns the first failure's message, or null.
+const char* check_common(bool pointers, int B, int C, int n, int S, const char* own, const Layout& L,
+                         const void* workspace) {
+  if (!pointers) return "null pointer";
+  if (!(B > 0 && C > 0 && n > 0 && S > 0)) return "non-positive shape";
+  if (S < 2) return "S must be at least 2 (the two taps of a row are loaded as a pair)";
+  if (!(S < 46341 && (long long)B * C * n * S * S < (1ll << 31))) return "maps of 2^31 elements or more";
+  if (B > 65535) return "more than 65535 images";
+  if (own) return own;
+  if (L.bytes <= 0) return "workspace of 2^31 bytes or more";
+  if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return "workspace must be 8-byte aligned";
+  return nullptr;
+}
+
+// The tile kernel's launch: grid (tiles, B), the partials where `L` puts them.
+template <bool SCORED>
+void launch_tile(const float* maps, int B, int C, int n, int S, const float* theta_inv, float* avg, void* workspace,
+                 const Layout& L, hipStream_t st) {
+  TileArgsOf<SCORED> A;
+  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg;
+  A.part_v = at<float>(workspace, L.part_v), A.part_i = at<int>(workspace, L.part_i);
+  if constexpr (SCORED) A.part_m = at<double>(workspace, L.part_m);
+  A.C = C, A.n = n, A.S = S;
+  hipLaunchKernelGGL(tta_tile_kernel<SCORED>, dim3(tiles_x(S) * tiles_y(S), B), dim3(kThreads), 0, st, A);
+}
+
 }  // namespace
 
-extern "C" int skp_tta_reduce_workspace(int B, int n, int S) {
-  if (B <= 0 || n <= 0 || S < 2) return -1;
-  const long long bytes = (long long)B * n * tiles_x(S) * tiles_y(S) * 8;
-  return bytes < (1ll << 31) ? (int)bytes : -1;
-}
+extern "C" int skp_tta_reduce_workspace(int B, int n, int S) { return (int)layout(B, n, S, kPlain, 1).bytes; }
 
 extern "C" int skp_tta_reduce(const float* maps, int B, int C, int n, int S, const float* theta_inv, float* pos,
                               float* avg, void* workspace, void* stream) {
-  SKP_CHECK_ARG(maps && theta_inv && pos && workspace, "null pointer");
-  SKP_CHECK_ARG(B > 0 && C > 0 && n > 0 && S > 0, "non-positive shape");
-  SKP_CHECK_ARG(S >= 2, "S must be at least 2 (the two taps of a row are loaded as a pair)");
-  SKP_CHECK_ARG(S < 46341 && (long long)B * C * n * S * S < (1ll << 31), "maps of 2^31 elements or more");
-  SKP_CHECK_ARG(B <= 65535, "more than 65535 images");
-  SKP_CHECK_ARG(skp_tta_reduce_workspace(B, n, S) > 0, "workspace of 2^31 bytes or more");
-  SKP_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
-  const int tiles = tiles_x(S) * tiles_y(S);
-  float* part_v = static_cast<float*>(workspace);
-  int* part_i = reinterpret_cast<int*>(part_v + (size_t)B * n * tiles);
+  const Layout L = layout(B, n, S, kPlain, 1);
+  const char* bad = check_common(maps && theta_inv && pos && workspace, B, C, n, S, nullptr, L, workspace);
+  SKP_CHECK_ARG(!bad, bad);
   hipStream_t st = as_stream(stream);
-  TileArgs A;
-  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg, A.part_v = part_v, A.part_i = part_i;
-  A.C = C, A.n = n, A.S = S;
-  hipLaunchKernelGGL(tta_tile_kernel<false>, dim3(tiles, B), dim3(kThreads), 0, st, A);
+  launch_tile<false>(maps, B, C, n, S, theta_inv, avg, workspace, L, st);
   SKP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tta_merge_kernel, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, tiles, S, pos);
+  hipLaunchKernelGGL(tta_merge_kernel<kPlain>, dim3(B * n), dim3(WAVE), 0, st, at<float>(workspace, L.part_v),
+                     at<int>(workspace, L.part_i), nullptr, tiles_x(S) * tiles_y(S), S, 1, 0, pos, nullptr, 0, nullptr,
+                     nullptr);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }
 
-// Per image and token: the (value, index) partials, then the mass partials, one of each per tile,
-// then the merged total (double) and peak index (int, padded to 8 bytes).
-extern "C" int skp_tta_reduce_scored_workspace(int B, int n, int S) {
-  if (B <= 0 || n <= 0 || S < 2) return -1;
-  const long long bytes = (long long)B * n * ((long long)tiles_x(S) * tiles_y(S) * 16 + 16);
-  return bytes < (1ll << 31) ? (int)bytes : -1;
-}
+extern "C" int skp_tta_reduce_scored_workspace(int B, int n, int S) { return (int)layout(B, n, S, kScored, 1).bytes; }
 
 extern "C" int skp_tta_reduce_scored(const float* maps, int B, int C, int n, int S, const float* theta_inv,
                                      float distance, float* pos, float* refined, float* scores, float* avg,
                                      void* workspace, void* stream) {
-  SKP_CHECK_ARG(maps && theta_inv && pos && refined && scores && workspace, "null pointer");
-  SKP_CHECK_ARG(B > 0 && C > 0 && n > 0 && S > 0, "non-positive shape");
-  SKP_CHECK_ARG(S >= 2, "S must be at least 2 (the two taps of a row are loaded as a pair)");
-  SKP_CHECK_ARG(S < 46341 && (long long)B * C * n * S * S < (1ll << 31), "maps of 2^31 elements or more");
-  SKP_CHECK_ARG(B <= 65535, "more than 65535 images");
-  SKP_CHECK_ARG(skp_tta_reduce_scored_workspace(B, n, S) > 0, "workspace of 2^31 bytes or more");
-  SKP_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
+  const Layout L = layout(B, n, S, kScored, 1);
+  const char* bad =
+      check_common(maps && theta_inv && pos && refined && scores && workspace, B, C, n, S, nullptr, L, workspace);
+  SKP_CHECK_ARG(!bad, bad);
   SKP_CHECK_ARG(distance > 0.0f && distance <= (float)kMaxDistance, "distance must be in (0, 16]");
-  const int tiles = tiles_x(S) * tiles_y(S);
-  const size_t parts = (size_t)B * n * tiles;
-  float* part_v = static_cast<float*>(workspace);
-  int* part_i = reinterpret_cast<int*>(part_v + parts);
-  double* part_m = reinterpret_cast<double*>(part_i + parts);
-  double* total = part_m + parts;
-  int* peak_i = reinterpret_cast<int*>(total + (size_t)B * n);
+  double* total = at<double>(workspace, L.total);
+  int* peak_i = at<int>(workspace, L.peak_i);
   hipStream_t st = as_stream(stream);
-  ScoredTileArgs A;
-  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg, A.part_v = part_v, A.part_i = part_i, A.part_m = part_m;
-  A.C = C, A.n = n, A.S = S;
-  hipLaunchKernelGGL(tta_tile_kernel<true>, dim3(tiles, B), dim3(kThreads), 0, st, A);
+  launch_tile<true>(maps, B, C, n, S, theta_inv, avg, workspace, L, st);
   SKP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tta_merge_scored_kernel, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, part_m, tiles, S, pos,
-                     scores, peak_i, total);
+  hipLaunchKernelGGL(tta_merge_kernel<kScored>, dim3(B * n), dim3(WAVE), 0, st, at<float>(workspace, L.part_v),
+                     at<int>(workspace, L.part_i), at<double>(workspace, L.part_m), tiles_x(S) * tiles_y(S), S, 1, 0, pos,
+                     scores, 3, peak_i, total);
   SKP_LAUNCH_CHECK();
   hipLaunchKernelGGL(tta_window_kernel, dim3(B * n), dim3(kThreads), 0, st, maps, theta_inv, C, n, S, distance, peak_i,
                      total, refined, scores);
@@ -579,40 +611,30 @@ extern "C" int skp_tta_reduce_scored(const float* maps, int B, int C, int n, int
   return SKP_OK;
 }
 
-// skp_tta_reduce's partials, then one linear index (int) per image, token and round.
 extern "C" int skp_tta_reduce_peaks_workspace(int B, int n, int S, int num, float radius2) {
-  if (num < 1 || num > kMaxPeaks || !(radius2 > 0.0f) || !std::isfinite(radius2)) return -1;
-  const int base = skp_tta_reduce_workspace(B, n, S);
-  if (base <= 0) return -1;
-  const long long bytes = base + (((long long)B * n * num * 4 + 7) & ~7ll);
-  return bytes < (1ll << 31) ? (int)bytes : -1;
+  if (!(radius2 > 0.0f) || !std::isfinite(radius2)) return -1;
+  return (int)layout(B, n, S, kPeaks, num).bytes;
 }
 
 extern "C" int skp_tta_reduce_peaks(const float* maps, int B, int C, int n, int S, const float* theta_inv, int num,
                                     float radius2, float* pos, float* values, float* avg, void* workspace,
                                     void* stream) {
-  SKP_CHECK_ARG(maps && theta_inv && pos && values && workspace, "null pointer");
-  SKP_CHECK_ARG(B > 0 && C > 0 && n > 0 && S > 0, "non-positive shape");
-  SKP_CHECK_ARG(S >= 2, "S must be at least 2 (the two taps of a row are loaded as a pair)");
-  SKP_CHECK_ARG(S < 46341 && (long long)B * C * n * S * S < (1ll << 31), "maps of 2^31 elements or more");
-  SKP_CHECK_ARG(B <= 65535, "more than 65535 images");
-  SKP_CHECK_ARG(num >= 1 && num <= kMaxPeaks, "num must be in [1, 16]");
-  SKP_CHECK_ARG(radius2 > 0.0f && std::isfinite(radius2), "radius2 must be positive and finite");
-  SKP_CHECK_ARG(skp_tta_reduce_peaks_workspace(B, n, S, num, radius2) > 0, "workspace of 2^31 bytes or more");
-  SKP_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
+  const char* own = !(num >= 1 && num <= kMaxPeaks)                ? "num must be in [1, 16]"
+                    : !(radius2 > 0.0f && std::isfinite(radius2)) ? "radius2 must be positive and finite"
+                                                                  : nullptr;
+  const Layout L = layout(B, n, S, kPeaks, num);
+  const char* bad = check_common(maps && theta_inv && pos && values && workspace, B, C, n, S, own, L, workspace);
+  SKP_CHECK_ARG(!bad, bad);
   const int tiles = tiles_x(S) * tiles_y(S);
   const int R = mask_box(radius2, S);
   const int slots =
       std::min(span_tiles(2 * R + 1, kTileH), tiles_y(S)) * std::min(span_tiles(2 * R + 1, kTileW), tiles_x(S));
   SKP_CHECK_ARG(num == 1 || (long long)B * n * slots < (1ll << 31), "masked-tile grid of 2^31 workgroups or more");
-  float* part_v = static_cast<float*>(workspace);
-  int* part_i = reinterpret_cast<int*>(part_v + (size_t)B * n * tiles);
-  int* picks = part_i + (size_t)B * n * tiles;
+  float* part_v = at<float>(workspace, L.part_v);
+  int* part_i = at<int>(workspace, L.part_i);
+  int* picks = at<int>(workspace, L.picks);
   hipStream_t st = as_stream(stream);
-  TileArgs A;
-  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg, A.part_v = part_v, A.part_i = part_i;
-  A.C = C, A.n = n, A.S = S;
-  hipLaunchKernelGGL(tta_tile_kernel<false>, dim3(tiles, B), dim3(kThreads), 0, st, A);
+  launch_tile<false>(maps, B, C, n, S, theta_inv, avg, workspace, L, st);
   SKP_LAUNCH_CHECK();
   for (int round = 0; round < num; ++round) {
     if (round) {
@@ -620,8 +642,8 @@ extern "C" int skp_tta_reduce_peaks(const float* maps, int B, int C, int n, int 
                          num, round, radius2, R, slots, picks, part_v, part_i);
       SKP_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(tta_merge_peaks_kernel, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, tiles, S, num, round,
-                       pos, values, picks);
+    hipLaunchKernelGGL(tta_merge_kernel<kPeaks>, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, nullptr, tiles, S, num,
+                       round, pos, values, 1, picks, nullptr);
     SKP_LAUNCH_CHECK();
   }
   return SKP_OK;

@@ -2127,7 +2127,34 @@ def render_sheet(images, maps=None, points=None, *, rows, cols, downscale=1, pad
 
 
 # --------------------------------------------------------------------------- A18 TTA reduce
-_TTA_WS = {}   # (device, B, n, S) -> workspace of skp_tta_reduce_workspace bytes
+_TTA_WS = {}   # (query name, device, query arguments) -> workspace of that query's bytes
+
+
+def _tta_inputs(op, maps, theta_inv):
+    """The checks every TTA reduce makes of its inputs -> (maps, theta_inv, B, C, n, S, device), both
+    tensors contiguous on ``maps``' device."""
+    _lib.require_device(maps, theta_inv)
+    if maps.dim() != 5 or maps.shape[-1] != maps.shape[-2]:
+        raise ValueError(f"{op}: maps must be (B, C, n, S, S), got {tuple(maps.shape)}")
+    maps = _c(maps)
+    B, C, n, S, _ = maps.shape
+    if tuple(theta_inv.shape) != (B, C, 2, 3):
+        raise ValueError(f"{op}: theta_inv must be ({B}, {C}, 2, 3), got {tuple(theta_inv.shape)}")
+    dev = maps.device
+    return maps, _c(theta_inv.to(dev)), B, C, n, S, dev
+
+
+def _tta_workspace(op, dev, B, n, S, num=None, radius2=None):
+    """The cached workspace of ``skp_<op>``, sized by ``skp_<op>_workspace``; ``num`` and ``radius2``
+    are the k-peak query's further arguments (the size does not depend on ``radius2``)."""
+    key = (op, dev, B, n, S, num)
+    ws = _TTA_WS.get(key)
+    if ws is None:
+        nbytes = getattr(_lib.lib(), f"skp_{op}_workspace")(B, n, S, *(() if num is None else (num, radius2)))
+        if nbytes <= 0:
+            raise ValueError(f"{op}: bad shape B={B}, n={n}, S={S}" + ("" if num is None else f", num={num}"))
+        ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    return ws
 
 
 def tta_reduce_bytes(B, C, n, S, avg=False):
@@ -2144,30 +2171,13 @@ def tta_reduce(maps, theta_inv, return_avg=False):
     average (B, n, S, S) when ``return_avg``, else None.  Bit-identical to ``affine_warp`` per
     copy, sums in copy order, the division, the NaN fix and ``find_max_pixel``.
     """
-    _lib.require_device(maps, theta_inv)
-    if maps.dim() != 5 or maps.shape[-1] != maps.shape[-2]:
-        raise ValueError(f"tta_reduce: maps must be (B, C, n, S, S), got {tuple(maps.shape)}")
-    maps = _c(maps)
-    B, C, n, S, _ = maps.shape
-    if tuple(theta_inv.shape) != (B, C, 2, 3):
-        raise ValueError(f"tta_reduce: theta_inv must be ({B}, {C}, 2, 3), got {tuple(theta_inv.shape)}")
-    dev = maps.device
-    th = _c(theta_inv.to(dev))
-    key = (dev, B, n, S)
-    ws = _TTA_WS.get(key)
-    if ws is None:
-        nbytes = _lib.lib().skp_tta_reduce_workspace(B, n, S)
-        if nbytes <= 0:
-            raise ValueError(f"tta_reduce: bad shape B={B}, n={n}, S={S}")
-        ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce", maps, theta_inv)
+    ws = _tta_workspace("tta_reduce", dev, B, n, S)
     pos = torch.empty(B, n, 2, device=dev, dtype=F32)
     avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
     with _timed("skp_tta_reduce", tta_reduce_bytes(B, C, n, S, return_avg)):
         call("skp_tta_reduce", ptr(maps), B, C, n, S, ptr(th), ptr(pos), ptr(avg), ptr(ws), stream(dev))
     return pos, avg
-
-
-_TTA_SCORED_WS = {}   # (device, B, n, S) -> workspace of skp_tta_reduce_scored_workspace bytes
 
 
 def tta_reduce_scored_bytes(B, C, n, S, distance=5, avg=False):
@@ -2187,25 +2197,11 @@ def tta_reduce_scored(maps, theta_inv, distance=5, return_avg=False):
     the peak over its whole mass) and the coverage (``[..., 2]``: the share of the C copies that
     saw the peak pixel).  The average is not written unless ``return_avg``.  ``0 < distance <= 16``.
     """
-    _lib.require_device(maps, theta_inv)
-    if maps.dim() != 5 or maps.shape[-1] != maps.shape[-2]:
-        raise ValueError(f"tta_reduce_scored: maps must be (B, C, n, S, S), got {tuple(maps.shape)}")
-    maps = _c(maps)
-    B, C, n, S, _ = maps.shape
-    if tuple(theta_inv.shape) != (B, C, 2, 3):
-        raise ValueError(f"tta_reduce_scored: theta_inv must be ({B}, {C}, 2, 3), got {tuple(theta_inv.shape)}")
+    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_scored", maps, theta_inv)
     distance = float(distance)
     if not 0.0 < distance <= 16.0:
         raise ValueError(f"tta_reduce_scored: distance must be in (0, 16], got {distance}")
-    dev = maps.device
-    th = _c(theta_inv.to(dev))
-    key = (dev, B, n, S)
-    ws = _TTA_SCORED_WS.get(key)
-    if ws is None:
-        nbytes = _lib.lib().skp_tta_reduce_scored_workspace(B, n, S)
-        if nbytes <= 0:
-            raise ValueError(f"tta_reduce_scored: bad shape B={B}, n={n}, S={S}")
-        ws = _TTA_SCORED_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    ws = _tta_workspace("tta_reduce_scored", dev, B, n, S)
     pos = torch.empty(B, n, 2, device=dev, dtype=F32)
     refined = torch.empty(B, n, 2, device=dev, dtype=F32)
     scores = torch.empty(B, n, 3, device=dev, dtype=F32)
@@ -2214,9 +2210,6 @@ def tta_reduce_scored(maps, theta_inv, distance=5, return_avg=False):
         call("skp_tta_reduce_scored", ptr(maps), B, C, n, S, ptr(th), distance, ptr(pos), ptr(refined), ptr(scores),
              ptr(avg), ptr(ws), stream(dev))
     return pos, refined, scores, avg
-
-
-_TTA_PEAKS_WS = {}   # (device, B, n, S, num) -> workspace of skp_tta_reduce_peaks_workspace bytes
 
 
 def tta_reduce_peaks_bytes(B, C, n, S, num, radius=None, avg=False):
@@ -2241,28 +2234,14 @@ def tta_reduce_peaks(maps, theta_inv, num, radius=None, return_avg=False):
     ``radius=None`` is the reference's 0.05 · S.  ``1 <= num <= 16``.  The average is not in memory
     unless ``return_avg``.
     """
-    _lib.require_device(maps, theta_inv)
-    if maps.dim() != 5 or maps.shape[-1] != maps.shape[-2]:
-        raise ValueError(f"tta_reduce_peaks: maps must be (B, C, n, S, S), got {tuple(maps.shape)}")
-    maps = _c(maps)
-    B, C, n, S, _ = maps.shape
-    if tuple(theta_inv.shape) != (B, C, 2, 3):
-        raise ValueError(f"tta_reduce_peaks: theta_inv must be ({B}, {C}, 2, 3), got {tuple(theta_inv.shape)}")
+    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_peaks", maps, theta_inv)
     num = int(num)
     if not 1 <= num <= 16:
         raise ValueError(f"tta_reduce_peaks: num must be in [1, 16], got {num}")
     radius2 = _radius2(S) if radius is None else float(radius) ** 2
     if not 0.0 < radius2 < float("inf"):
         raise ValueError(f"tta_reduce_peaks: radius must be positive and finite, got {radius}")
-    dev = maps.device
-    th = _c(theta_inv.to(dev))
-    key = (dev, B, n, S, num)
-    ws = _TTA_PEAKS_WS.get(key)
-    if ws is None:
-        nbytes = _lib.lib().skp_tta_reduce_peaks_workspace(B, n, S, num, radius2)
-        if nbytes <= 0:
-            raise ValueError(f"tta_reduce_peaks: bad shape B={B}, n={n}, S={S}, num={num}")
-        ws = _TTA_PEAKS_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    ws = _tta_workspace("tta_reduce_peaks", dev, B, n, S, num, radius2)
     pos = torch.empty(B, n, num, 2, device=dev, dtype=F32)
     values = torch.empty(B, n, num, device=dev, dtype=F32)
     avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None

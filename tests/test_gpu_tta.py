@@ -10,37 +10,16 @@ import pytest
 import torch
 
 import tta_ref
+import tta_tiny
+from tta_tiny import AUG, DEV, N_TOK, R, S_UP, predict as _predict, seed as _seed
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-
-
-def _sequential(maps, theta):
-    """The existing ops, one copy at a time: acc = acc + affine_warp(copy) for the maps and for
-    ones, the division, NaN -> 0, find_max_pixel."""
-    from stablekeypoints_amd import ops
-    B, C, n, S, _ = maps.shape
-    ones = torch.ones(1, n, S, S, device=maps.device)
-    avg = torch.empty(B, n, S, S, device=maps.device)
-    pos = torch.empty(B, n, 2, device=maps.device)
-    for b in range(B):
-        acc = torch.zeros(n, S, S, device=maps.device)
-        num = torch.zeros(n, S, S, device=maps.device)
-        for c in range(C):
-            acc = acc + ops.affine_warp(maps[b, c][None], theta[b, c][None])[0]
-            num = num + ops.affine_warp(ones, theta[b, c][None])[0]
-        a = acc / num
-        a[a != a] = 0
-        avg[b] = a
-        pos[b] = ops.find_max_pixel(a)
-    return pos, avg
 
 
 def _chunked(maps, theta):
@@ -62,7 +41,7 @@ def case(request):
     from stablekeypoints_amd import ops
     maps_np, theta_np, finite = tta_ref.make_case(request.param)
     maps, theta = torch.from_numpy(maps_np).to(DEV), torch.from_numpy(theta_np).to(DEV)
-    seq_pos, seq_avg = _sequential(maps, theta)
+    seq_pos, seq_avg, _ = tta_tiny.sequential(maps, theta)
     ref_pos, ref_avg, ref_num = tta_ref.tta_ref(np.where(finite[:, None, :, None, None], maps_np, 0.0), theta_np)
     pos, avg = ops.tta_reduce(maps, theta, return_avg=True)
     pos_only, none = ops.tta_reduce(maps, theta)
@@ -127,35 +106,9 @@ def test_tta_reduce_rejects_bad_shapes():
 
 
 # ------------------------------------------------------------------------------------------ end to end
-R, S_UP, N_TOK = 32, 64, 16
-AUG = dict(augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1))
-
-
 @pytest.fixture(scope="module")
 def tiny():
-    from stablekeypoints_amd import ptp_utils
-    from stablekeypoints_amd.sd import TINY_CONFIG, TINY_IMAGE, build_sd15
-    ldm = build_sd15(seed=0, config=TINY_CONFIG).to(DEV)
-    ldm.feature_upsample_res = R
-    ctl = ptp_utils.AttentionStore(early_exit=True)
-    ptp_utils.register_attention_control(ldm.unet, ctl, feature_upsample_res=R)
-    g = torch.Generator().manual_seed(11)
-    images = torch.rand(2, 3, TINY_IMAGE, TINY_IMAGE, generator=g)
-    ctx = torch.randn(1, N_TOK, 32, generator=g).to(DEV)
-    return ldm, {torch.device(DEV): ctl}, images, ctx, torch.tensor([3, 7, 0, 12, 5])
-
-
-def _seed():
-    torch.manual_seed(123)
-    torch.cuda.manual_seed(123)
-
-
-def _predict(tiny, images, **kw):
-    from stablekeypoints_amd import eval as ev
-    ldm, controllers, _, ctx, indices = tiny
-    _seed()
-    return ev.predict_keypoints(ldm, images, ctx, indices, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
-                                upscale_size=S_UP, **AUG, **kw)
+    return tta_tiny.build_tiny()
 
 
 def test_predict_keypoints_tiny(tiny):

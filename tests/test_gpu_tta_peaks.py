@@ -14,10 +14,11 @@ import torch
 
 import tta_peaks_ref
 import tta_ref
+import tta_tiny
+from tta_tiny import DEV, N_TOK, R, S_UP
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 NUMS = (1, 2, 3, 4)
 
 
@@ -162,31 +163,13 @@ def test_tta_reduce_peaks_rejects_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------ end to end
-R, S_UP, N_TOK = 32, 64, 16
-AUG = dict(augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1))
-
-
 @pytest.fixture(scope="module")
 def tiny():
-    from stablekeypoints_amd import ptp_utils
-    from stablekeypoints_amd.sd import TINY_CONFIG, TINY_IMAGE, build_sd15
-    ldm = build_sd15(seed=0, config=TINY_CONFIG).to(DEV)
-    ldm.feature_upsample_res = R
-    ctl = ptp_utils.AttentionStore(early_exit=True)
-    ptp_utils.register_attention_control(ldm.unet, ctl, feature_upsample_res=R)
-    g = torch.Generator().manual_seed(11)
-    images = torch.rand(2, 3, TINY_IMAGE, TINY_IMAGE, generator=g)
-    ctx = torch.randn(1, N_TOK, 32, generator=g).to(DEV)
-    return ldm, {torch.device(DEV): ctl}, images, ctx, torch.tensor([3, 7, 0, 12, 5])
+    return tta_tiny.build_tiny()
 
 
 def _predict(tiny, **kw):
-    from stablekeypoints_amd import eval as ev
-    ldm, controllers, images, ctx, indices = tiny
-    torch.manual_seed(123)
-    torch.cuda.manual_seed(123)
-    return ev.predict_keypoints(ldm, images, ctx, indices, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
-                                upscale_size=S_UP, augmentation_iterations=3, **AUG, **kw)
+    return tta_tiny.predict(tiny, tiny[2], augmentation_iterations=3, **kw)
 
 
 def test_predict_keypoints_subjects_tiny(tiny):

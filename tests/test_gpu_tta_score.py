@@ -16,38 +16,16 @@ import torch
 
 import tta_ref
 import tta_score_ref
+import tta_tiny
+from tta_tiny import DEV, N_TOK, R, S_UP, predict as _predict, sequential as _sequential
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-
-
-def _sequential(maps, theta):
-    """The existing ops, one copy at a time; returns (pos, avg, num (B, S, S))."""
-    from stablekeypoints_amd import ops
-    B, C, n, S, _ = maps.shape
-    ones = torch.ones(1, n, S, S, device=maps.device)
-    avg = torch.empty(B, n, S, S, device=maps.device)
-    nums = torch.empty(B, S, S, device=maps.device)
-    pos = torch.empty(B, n, 2, device=maps.device)
-    for b in range(B):
-        acc = torch.zeros(n, S, S, device=maps.device)
-        num = torch.zeros(n, S, S, device=maps.device)
-        for c in range(C):
-            acc = acc + ops.affine_warp(maps[b, c][None], theta[b, c][None])[0]
-            num = num + ops.affine_warp(ones, theta[b, c][None])[0]
-        a = acc / num
-        a[a != a] = 0
-        avg[b] = a
-        nums[b] = num[0]
-        pos[b] = ops.find_max_pixel(a)
-    return pos, avg, nums
 
 
 # (kind, shape, distance): the shared shapes at 5, the planted ones at 5, one of them at 1.5 and 16
@@ -221,31 +199,9 @@ def test_tta_reduce_scored_rejects_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------ end to end
-R, S_UP, N_TOK = 32, 64, 16
-AUG = dict(augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1))
-
-
 @pytest.fixture(scope="module")
 def tiny():
-    from stablekeypoints_amd import ptp_utils
-    from stablekeypoints_amd.sd import TINY_CONFIG, TINY_IMAGE, build_sd15
-    ldm = build_sd15(seed=0, config=TINY_CONFIG).to(DEV)
-    ldm.feature_upsample_res = R
-    ctl = ptp_utils.AttentionStore(early_exit=True)
-    ptp_utils.register_attention_control(ldm.unet, ctl, feature_upsample_res=R)
-    g = torch.Generator().manual_seed(11)
-    images = torch.rand(2, 3, TINY_IMAGE, TINY_IMAGE, generator=g)
-    ctx = torch.randn(1, N_TOK, 32, generator=g).to(DEV)
-    return ldm, {torch.device(DEV): ctl}, images, ctx, torch.tensor([3, 7, 0, 12, 5])
-
-
-def _predict(tiny, images, **kw):
-    from stablekeypoints_amd import eval as ev
-    ldm, controllers, _, ctx, indices = tiny
-    torch.manual_seed(123)
-    torch.cuda.manual_seed(123)
-    return ev.predict_keypoints(ldm, images, ctx, indices, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
-                                upscale_size=S_UP, **AUG, **kw)
+    return tta_tiny.build_tiny()
 
 
 def test_predict_keypoints_scores_tiny(tiny, monkeypatch):

@@ -113,3 +113,20 @@ def test_tta_reduce_rejects_bad_arguments_without_gpu():
     assert L.skp_tta_reduce_workspace(1, 10, 512) == 10 * (8 * 128) * 8
     assert L.skp_tta_reduce_workspace(2, 5, 37) >= 2 * 5 * 8
     assert L.skp_tta_reduce_workspace(0, 1, 8) == -1 and L.skp_tta_reduce_workspace(1, 1, -3) == -1
+
+
+@pytest.mark.parametrize("B,n,S", [(1, 1, 2), (2, 5, 37), (1, 10, 512), (4, 10, 512)])
+def test_workspace_queries_equal_their_closed_forms(B, n, S):
+    """The three layouts by value, T = ceil(S/64)·ceil(S/4) tiles per plane: a (value, index) pair per
+    image, token and tile; scored adds a double per tile and 16 bytes per image and token; peaks
+    adds an int per image, token and round, rounded up to 8 bytes."""
+    from stablekeypoints_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libskp.so not built")
+    L = _lib.lib()
+    T = -(-S // 64) * -(-S // 4)
+    assert L.skp_tta_reduce_workspace(B, n, S) == 8 * B * n * T
+    assert L.skp_tta_reduce_scored_workspace(B, n, S) == B * n * (16 * T + 16)
+    r2 = float(np.float32((0.05 * S) ** 2))
+    for num in (1, 3, 16):
+        assert L.skp_tta_reduce_peaks_workspace(B, n, S, num, r2) == 8 * B * n * T + (4 * B * n * num + 7) // 8 * 8
