@@ -529,6 +529,28 @@ int skp_tta_reduce_peaks_workspace(int B, int n, int S, int num, float radius2);
 int skp_tta_reduce_peaks(const float* maps, int B, int C, int n, int S, const float* theta_inv, int num,
                          float radius2, float* pos, float* values, float* avg, void* workspace, void* stream);
 
+/* The entropy TTA reduce: skp_tta_reduce (eval.py:327-355, then eval.find_max_pixel, eval.py:39-60)
+ * and, in the same pass and without the average in memory, the key eval.find_corresponding_points
+ * (eval.py:159-195) ranks tokens by: the Shannon entropy of the softmax of each averaged plane.
+ *   pos, avg: skp_tta_reduce's, bit for bit.  entropy (B, n) double.  With a the fp32 average of
+ *   image b and token t (after NaN -> 0), z = (double)scale · (double)a over its S² pixels and
+ *   m = max z:   entropy[b,t] = −Σ p·log p,  p = e^{z−m} / Σ e^{z−m}
+ *              = log S0 − T / S0,  S0 = Σ e^{z−m},  T = Σ (z−m)·e^{z−m},
+ *   in double; a pixel with e^{z−m} == 0 (a = −inf among them) adds 0 to T, and a maximum of +inf
+ *   gives NaN.  A plane of equal values gives log S².
+ * Two launches, no atomics: the tile kernel (grid tiles × B × chunks of 10 tokens) leaves (S0, T)
+ * about each tile's maximum beside its partial — lanes about their wave's maximum in a fixed tree,
+ * then the four waves in order, rescaled by e^{scale·(m_wave − m_tile)} — and the merge takes in the
+ * tiles about the plane's maximum the same way (lane k tiles k, k + 64, … in order, then the tree).
+ * Deterministic, and the same whether or not avg is asked for.
+ * workspace: skp_tta_reduce_entropy_workspace(B, n, S) bytes (−1 on a bad shape), 8-B aligned:
+ * skp_tta_reduce's partials and two doubles per image, token and tile.
+ * Rejected before any launch: what skp_tta_reduce rejects, a null entropy, a scale that is not
+ * positive and finite, n > 655350.                                                             */
+int skp_tta_reduce_entropy_workspace(int B, int n, int S);
+int skp_tta_reduce_entropy(const float* maps, int B, int C, int n, int S, const float* theta_inv, float scale,
+                           float* pos, double* entropy, float* avg, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,8 @@ _SIGS = {
     "skp_tta_reduce_scored": [_p, _c_int, _c_int, _c_int, _c_int, _p, _c_float, _p, _p, _p, _p, _p, _p],
     "skp_tta_reduce_peaks_workspace": [_c_int, _c_int, _c_int, _c_int, _c_float],
     "skp_tta_reduce_peaks": [_p, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _c_float, _p, _p, _p, _p, _p],
+    "skp_tta_reduce_entropy_workspace": [_c_int, _c_int, _c_int],
+    "skp_tta_reduce_entropy": [_p, _c_int, _c_int, _c_int, _c_int, _p, _c_float, _p, _p, _p, _p, _p],
     "skp_version": [],
 }
 

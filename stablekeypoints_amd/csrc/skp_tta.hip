@@ -32,8 +32,20 @@
 // of row_argmax_masked, skp_select.hip) and overwrites their partials in place; then the merge
 // again.  2 + 2(num − 1) launches, no atomics.
 //
+// The entropy reduce (skp_tta_reduce_entropy) adds the Shannon entropy of softmax(scale · average)
+// over the plane (eval.find_corresponding_points, eval.py:159-195, ranks tokens by it), again without
+// the average in memory.  One pass: H = log S0 − T / S0 with S0 = Σ e^{z−m} and T = Σ (z−m)·e^{z−m},
+// z = scale · a, about a maximum m.  A wave sums about its own maximum; the tile kernel's entropy
+// instantiation combines its four waves about the tile's maximum and leaves (S0, T) beside the
+// partial, and the merge's kEntropy instantiation combines the tiles about the plane's maximum
+// (entropy_add: a partial about m_k enters sums about m >= m_k scaled by e^{scale·(m_k−m)}).  All in
+// double, every order fixed: lanes in the wave tree, waves in wave order, tiles k, k + 64, … per
+// lane and then the wave tree.  Its grid has a third dimension over chunks of kTok tokens: the
+// selection reduces every token of an embedding (n = 500 at S = 128 is 64 tiles per image).  Two
+// launches, no atomics.
+//
 // Host side: layout() is the one statement of the workspace (the queries return its size, the entry
-// points take their pointers from its offsets), check_common() the checks the three entry points
+// points take their pointers from its offsets), check_common() the checks the entry points
 // share, launch_tile() the tile kernel's launch.
 #include <algorithm>
 #include <cmath>
@@ -188,12 +200,38 @@ struct ScoredTileArgs : TileArgs {
 };
 template <bool SCORED>
 using TileArgsOf = std::conditional_t<SCORED, ScoredTileArgs, TileArgs>;
+struct EntropyTileArgs : TileArgs {
+  double* part_s0;          // (B, n, tiles): Σ e^{z−m} and Σ (z−m)·e^{z−m} over the tile, z = scale · a,
+  double* part_t;           // m = scale · the tile's maximum (part_v)
+  float scale;
+};
+enum Tile { kTilePlain, kTileScored, kTileEntropy };
+template <Tile K>
+using ArgsOfTile = std::conditional_t<K == kTileEntropy, EntropyTileArgs, TileArgsOf<K == kTileScored>>;
+
+// Sums (s0, t) about the maximum m take in a partial (sk, tk) about mk <= m:
+// Σ (z−m)·e^{z−m} = e^d · (Σ (z−mk)·e^{z−mk} + d · Σ e^{z−mk}) with d = scale · (mk − m) <= 0.  A
+// partial with no pixel above −inf (mk = −inf: sk = tk = 0) and one that e^d takes to 0 add nothing,
+// which is the limit; mk = m = +inf gives d = NaN and NaN sums.
+__device__ __forceinline__ void entropy_add(double& s0, double& t, float mk, double sk, double tk, float m,
+                                            float scale) {
+  if (!(mk > -INFINITY)) return;
+  const double d = (double)scale * ((double)mk - (double)m);
+  const double r = exp(d);
+  if (r == 0.0) return;
+  s0 += sk * r;
+  t += (tk + d * sk) * r;
+}
 
 // Tokens t0 … t0 + NT − 1 of this thread's pixel: one pass over the copies, the sums in registers.
 // SCORED: each token's averaged value also goes, as it is produced, into the tile's mass: lane
 // value (0 outside the plane) -> wave tree -> the four waves in order, all in double.
-template <int NT, bool SCORED>
-__device__ __forceinline__ void tile_pass(const TileArgsOf<SCORED>& A, int t0, int b, int x, int y, bool inside, int p,
+// kTileEntropy: once the pass's averages exist, token by token: each lane's e = exp(z − m) about its
+// wave's maximum (the double exp; a pixel outside the plane or at −inf has e = 0, and e = 0 adds 0
+// to T), S0 and T through the wave tree into s_m[j] and s_m[kTok + j], then the four waves in order
+// about the tile's maximum.
+template <int NT, Tile K>
+__device__ __forceinline__ void tile_pass(const ArgsOfTile<K>& A, int t0, int b, int x, int y, bool inside, int p,
                                           float (*s_v)[kWaves], int (*s_i)[kWaves], double (*s_m)[kWaves]) {
   const int S = A.S, SS = S * S;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -234,14 +272,29 @@ __device__ __forceinline__ void tile_pass(const TileArgsOf<SCORED>& A, int t0, i
   }
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
-    if constexpr (SCORED) {
+    if constexpr (K == kTileScored) {
       const double m = wave_sum_tree(inside ? (double)bv[j] : 0.0);
       if (lane == 0) s_m[j][wid] = m;
     }
+    const float a = bv[j];
     wave_best(bv[j], bi[j]);
     if (lane == 0) {
       s_v[j][wid] = bv[j];
       s_i[j][wid] = bi[j];
+    }
+    if constexpr (K == kTileEntropy) {
+      double e = 0.0, t = 0.0;
+      if (a > -INFINITY) {
+        const double d = (double)A.scale * ((double)a - (double)bv[j]);
+        e = exp(d);
+        t = e == 0.0 ? 0.0 : d * e;
+      }
+      e = wave_sum_tree(e);
+      t = wave_sum_tree(t);
+      if (lane == 0) {
+        s_m[j][wid] = e;
+        s_m[kTok + j][wid] = t;
+      }
     }
   }
   __syncthreads();
@@ -258,18 +311,46 @@ __device__ __forceinline__ void tile_pass(const TileArgsOf<SCORED>& A, int t0, i
     const size_t o = ((size_t)b * A.n + t0 + j) * gridDim.x + blockIdx.x;
     A.part_v[o] = v;
     A.part_i[o] = i;
-    if constexpr (SCORED) {
+    if constexpr (K == kTileScored) {
       double m = s_m[j][0];
 #pragma unroll
       for (int k = 1; k < kWaves; ++k) m += s_m[j][k];
       A.part_m[o] = m;
     }
+    if constexpr (K == kTileEntropy) {
+      double s0 = 0.0, t = 0.0;
+#pragma unroll
+      for (int k = 0; k < kWaves; ++k) entropy_add(s0, t, s_v[j][k], s_m[j][k], s_m[kTok + j][k], v, A.scale);
+      A.part_s0[o] = s0;
+      A.part_t[o] = t;
+    }
   }
   __syncthreads();
 }
 
-// grid (tiles_x · tiles_y, B).  The tokens go in passes of kTok, the rest in passes of 8, 4, 2, 1
-// (compile-time counts: no branch between a pass's loads).  Four waves per SIMD are asked for, not
+// Tokens t0 … t1 − 1 of this thread's pixel: in passes of kTok, the rest in passes of 8, 4, 2, 1
+// (compile-time counts: no branch between a pass's loads).
+template <Tile K>
+__device__ __forceinline__ void tile_tokens(const ArgsOfTile<K>& A, int t0, int t1, int b, int x, int y, bool inside,
+                                            int p, float (*s_v)[kWaves], int (*s_i)[kWaves], double (*s_m)[kWaves]) {
+  for (; t0 + kTok <= t1; t0 += kTok) tile_pass<kTok, K>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
+  const int rest = t1 - t0;   // < kTok <= 15
+  if (rest & 8) {
+    tile_pass<8, K>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
+    t0 += 8;
+  }
+  if (rest & 4) {
+    tile_pass<4, K>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
+    t0 += 4;
+  }
+  if (rest & 2) {
+    tile_pass<2, K>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
+    t0 += 2;
+  }
+  if (rest & 1) tile_pass<1, K>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
+}
+
+// grid (tiles_x · tiles_y, B), every token in turn (tile_tokens).  Four waves per SIMD are asked for, not
 // eight: a pass holds 4·kTok loaded values, and one image of 512² is four waves per SIMD anyway.
 template <bool SCORED>
 __global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgsOf<SCORED> A) {
@@ -281,22 +362,23 @@ __global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgsOf<
   tile_pixel(tile % tiles_x(S), tile / tiles_x(S), x, y);
   const bool inside = x < S && y < S;
   const int p = inside ? y * S + x : 0;
-  int t0 = 0;
-  for (; t0 + kTok <= A.n; t0 += kTok) tile_pass<kTok, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
-  const int rest = A.n - t0;   // < kTok <= 15
-  if (rest & 8) {
-    tile_pass<8, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
-    t0 += 8;
-  }
-  if (rest & 4) {
-    tile_pass<4, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
-    t0 += 4;
-  }
-  if (rest & 2) {
-    tile_pass<2, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
-    t0 += 2;
-  }
-  if (rest & 1) tile_pass<1, SCORED>(A, t0, b, x, y, inside, p, s_v, s_i, s_m);
+  tile_tokens<SCORED ? kTileScored : kTilePlain>(A, 0, A.n, b, x, y, inside, p, s_v, s_i, s_m);
+}
+
+// The entropy reduce's tile kernel: grid (tiles_x · tiles_y, B, ⌈n / kTok⌉), workgroup z takes the
+// tokens of chunk z, so that a selection over a whole embedding (n = 500, S = 128: 64 tiles per
+// image) fills the device.  The partial of (image, token, tile) is where the other reduces have it.
+__global__ __launch_bounds__(kThreads, 4) void tta_tile_entropy_kernel(const EntropyTileArgs A) {
+  __shared__ float s_v[kTok][kWaves];
+  __shared__ int s_i[kTok][kWaves];
+  __shared__ double s_m[2 * kTok][kWaves];
+  const int b = blockIdx.y, tile = blockIdx.x, S = A.S;
+  int x, y;
+  tile_pixel(tile % tiles_x(S), tile / tiles_x(S), x, y);
+  const bool inside = x < S && y < S;
+  const int p = inside ? y * S + x : 0;
+  const int t0 = blockIdx.z * kTok;
+  tile_tokens<kTileEntropy>(A, t0, min(t0 + kTok, A.n), b, x, y, inside, p, s_v, s_i, s_m);
 }
 
 // The merge of all three reduces, one wave per (image, token): the best of its `parts` partials
@@ -304,7 +386,10 @@ __global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgsOf<
 // and round 0.  The winning value goes to `value` (stride `value_stride`: the scores' first column,
 // or the peaks' values) and its linear index to `index` (the window kernel's peak, or the pick the
 // next round masks) where they are given.  kScored: the mass partials are summed too, in a fixed
-// order (lane k takes partials k, k + 64, … in order, then the wave tree), into `total`.
+// order (lane k takes partials k, k + 64, … in order, then the wave tree), into `total`.  kEntropy:
+// part_m and part_t hold the tiles' (S0, T) about their own maxima; once every lane has the plane's
+// maximum, lane k takes in partials k, k + 64, … in order (entropy_add), the wave tree sums both, and
+// `total` gets log S0 − T / S0.
 //
 // kPeaks reduces in torch.argmax's order (argmax_better: a masked +inf is NaN, and NaN wins), which
 // its rounds after the first need.  Round-0 partials hold no NaN (the tile kernel turns NaN into 0
@@ -312,13 +397,14 @@ __global__ __launch_bounds__(kThreads, 4) void tta_tile_kernel(const TileArgsOf<
 // values the lower index, a total order, so every variant's round 0 picks the same partial.  The
 // NaN-free reduction stays for kPlain and kScored because it is faster there: measured in their
 // place, the argmax-order merge took 8.3 µs against 6.9 µs (640 waves) and 9.1 against 7.8 (2560).
-enum Variant { kPlain, kScored, kPeaks };
+enum Variant { kPlain, kScored, kPeaks, kEntropy };
 template <Variant V>
 __global__ __launch_bounds__(WAVE) void tta_merge_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i,
                                                          const double* __restrict__ part_m, int parts, int S, int num,
                                                          int round, float* __restrict__ pos, float* __restrict__ value,
                                                          int value_stride, int* __restrict__ index,
-                                                         double* __restrict__ total) {
+                                                         double* __restrict__ total,
+                                                         const double* __restrict__ part_t, float scale) {
   constexpr bool MASS = V == kScored, NAN_WINS = V == kPeaks;
   const size_t o = (size_t)blockIdx.x * parts;
   float v = -INFINITY;
@@ -334,6 +420,13 @@ __global__ __launch_bounds__(WAVE) void tta_merge_kernel(const float* __restrict
   if constexpr (NAN_WINS) wave_argmax(v, i);
   else wave_best(v, i);
   if constexpr (MASS) m = wave_sum_tree(m);
+  [[maybe_unused]] double t = 0.0;
+  if constexpr (V == kEntropy) {
+    for (int k = threadIdx.x; k < parts; k += WAVE)
+      entropy_add(m, t, part_v[o + k], part_m[o + k], part_t[o + k], v, scale);
+    m = wave_sum_tree(m);
+    t = wave_sum_tree(t);
+  }
   if (threadIdx.x == 0) {
     const size_t q = (size_t)blockIdx.x * num + round;
     pos[2 * q] = (float)(i / S) + 0.5f;
@@ -341,6 +434,7 @@ __global__ __launch_bounds__(WAVE) void tta_merge_kernel(const float* __restrict
     if (value) value[q * value_stride] = v;
     if (index) index[q] = i;
     if constexpr (MASS) total[blockIdx.x] = m;
+    if constexpr (V == kEntropy) total[blockIdx.x] = log(m) - t / m;
   }
 }
 
@@ -505,9 +599,10 @@ inline int mask_box(float radius2, int S) {
 //   part_v  P floats, part_i  P ints                  (all variants; 8·P bytes)
 //   part_m  P doubles, total  B·n doubles, peak_i  B·n ints in B·n·8 bytes    (scored)
 //   picks   B·n·num ints, rounded up to 8 bytes                               (peaks)
+//   part_m  P doubles (the tiles' S0), part_t  P doubles (their T)            (entropy)
 // `bytes` is −1 for a shape no reduce takes (the queries' answer) and for 2^31 bytes or more.
 struct Layout {
-  long long part_v, part_i, part_m, total, peak_i, picks;   // byte offsets; 0 where the variant has none
+  long long part_v, part_i, part_m, part_t, total, peak_i, picks;   // byte offsets; 0 where the variant has none
   long long bytes;
 };
 Layout layout(int B, int n, int S, Variant variant, int num) {
@@ -530,6 +625,10 @@ Layout layout(int B, int n, int S, Variant variant, int num) {
     L.total = take(8 * bt);
     L.peak_i = take(8 * bt);
   }
+  if (variant == kEntropy) {
+    L.part_m = take(8 * parts);
+    L.part_t = take(8 * parts);
+  }
   if (variant == kPeaks) L.picks = take((4 * bt * num + 7) & ~7ll);
   if (end < (1ll << 31)) L.bytes = end;
   return L;
@@ -539,7 +638,7 @@ T* at(void* workspace, long long offset) {
   return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset);
 }
 
-// The checks the three entry points share, in the order each of them always made them; `own` is
+// The checks the entry points share, in the order each of them always made them; `own` is
 // the message of the variant's failed checks that come before the workspace's (num and radius2 of
 // the k-peak reduce), or null.  Returns the first failure's message, or null.
 const char* check_common(bool pointers, int B, int C, int n, int S, const char* own, const Layout& L,
@@ -581,7 +680,7 @@ extern "C" int skp_tta_reduce(const float* maps, int B, int C, int n, int S, con
   SKP_LAUNCH_CHECK();
   hipLaunchKernelGGL(tta_merge_kernel<kPlain>, dim3(B * n), dim3(WAVE), 0, st, at<float>(workspace, L.part_v),
                      at<int>(workspace, L.part_i), nullptr, tiles_x(S) * tiles_y(S), S, 1, 0, pos, nullptr, 0, nullptr,
-                     nullptr);
+                     nullptr, nullptr, 0.0f);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }
@@ -603,7 +702,7 @@ extern "C" int skp_tta_reduce_scored(const float* maps, int B, int C, int n, int
   SKP_LAUNCH_CHECK();
   hipLaunchKernelGGL(tta_merge_kernel<kScored>, dim3(B * n), dim3(WAVE), 0, st, at<float>(workspace, L.part_v),
                      at<int>(workspace, L.part_i), at<double>(workspace, L.part_m), tiles_x(S) * tiles_y(S), S, 1, 0, pos,
-                     scores, 3, peak_i, total);
+                     scores, 3, peak_i, total, nullptr, 0.0f);
   SKP_LAUNCH_CHECK();
   hipLaunchKernelGGL(tta_window_kernel, dim3(B * n), dim3(kThreads), 0, st, maps, theta_inv, C, n, S, distance, peak_i,
                      total, refined, scores);
@@ -643,8 +742,33 @@ extern "C" int skp_tta_reduce_peaks(const float* maps, int B, int C, int n, int 
       SKP_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(tta_merge_kernel<kPeaks>, dim3(B * n), dim3(WAVE), 0, st, part_v, part_i, nullptr, tiles, S, num,
-                       round, pos, values, 1, picks, nullptr);
+                       round, pos, values, 1, picks, nullptr, nullptr, 0.0f);
     SKP_LAUNCH_CHECK();
   }
+  return SKP_OK;
+}
+
+extern "C" int skp_tta_reduce_entropy_workspace(int B, int n, int S) { return (int)layout(B, n, S, kEntropy, 1).bytes; }
+
+extern "C" int skp_tta_reduce_entropy(const float* maps, int B, int C, int n, int S, const float* theta_inv,
+                                      float scale, float* pos, double* entropy, float* avg, void* workspace,
+                                      void* stream) {
+  const char* own = !(scale > 0.0f && std::isfinite(scale)) ? "scale must be positive and finite" : nullptr;
+  const Layout L = layout(B, n, S, kEntropy, 1);
+  const char* bad = check_common(maps && theta_inv && pos && entropy && workspace, B, C, n, S, own, L, workspace);
+  SKP_CHECK_ARG(!bad, bad);
+  const int tiles = tiles_x(S) * tiles_y(S), chunks = (n + kTok - 1) / kTok;
+  SKP_CHECK_ARG(chunks <= 65535, "more than 65535 chunks of tokens");
+  EntropyTileArgs A;
+  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg;
+  A.part_v = at<float>(workspace, L.part_v), A.part_i = at<int>(workspace, L.part_i);
+  A.part_s0 = at<double>(workspace, L.part_m), A.part_t = at<double>(workspace, L.part_t);
+  A.C = C, A.n = n, A.S = S, A.scale = scale;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(tta_tile_entropy_kernel, dim3(tiles, B, chunks), dim3(kThreads), 0, st, A);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tta_merge_kernel<kEntropy>, dim3(B * n), dim3(WAVE), 0, st, A.part_v, A.part_i, A.part_s0, tiles,
+                     S, 1, 0, pos, nullptr, 0, nullptr, entropy, A.part_t, scale);
+  SKP_LAUNCH_CHECK();
   return SKP_OK;
 }

@@ -10,6 +10,9 @@ keypoints from it and scores them with the reference's five metrics (``keypoint_
 captures and the whole TTA reduce (inverse warps, sums, ratio, argmax) in one kernel,
 ``skp_tta_reduce``; with ``num_subjects`` = k > 1 also the k peaks per token of
 ``find_k_max_pixels`` on the average, from ``skp_tta_reduce_peaks``.
+``find_corresponding_points`` (``:159-195``) picks the tokens whose maps are jointly sharpest on a
+set of images; ``correspond_images`` (extra) does so on the TTA averages of unlabelled images, with
+each average's argmax and softmax entropy from ``skp_tta_reduce_entropy``.
 """
 import collections
 import contextlib
@@ -342,3 +345,127 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
     if k > 1:
         out.append(KeypointPeaks(torch.cat(pks) / S, torch.cat(vals)))
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def _rank_ascending(keys, k):
+    """The first ``k`` of a stable ascending argsort of (N,) float64 device keys, NaN last
+    (skp_topk_keys): (k,) int64."""
+    from ._lib import call, ptr, stream
+    N = keys.shape[0]
+    if N > 8192:
+        raise ValueError(f"at most 8192 tokens can be ranked, got {N}")
+    out = torch.empty(k, device=keys.device, dtype=torch.int64)
+    if k > 0:
+        call("skp_topk_keys", ptr(keys), 1, N, k, ptr(out), stream(keys.device))
+    return out
+
+
+def _sum_in_order(per_image):
+    """(M, N) -> (N,): image 0's row, then image 1's added, and so on (a fixed order)."""
+    total = per_image[0].clone()
+    for i in range(1, per_image.shape[0]):
+        total += per_image[i]
+    return total
+
+
+@torch.no_grad()
+def find_corresponding_points(maps, num_points=10):
+    """eval.py:159-195: the ``num_points`` tokens whose maps are jointly sharpest on these images.
+
+    ``maps`` (num_images, num_tokens, h, w) on the device.  Per image and token the entropy of
+    ``softmax(map)`` (``ops.entropy_keys_batch``: the reference's fp32 arithmetic, accumulated in
+    double), summed over the images image by image; the tokens with the lowest sums, ascending, ties
+    by index and NaN last (skp_topk_keys); ``find_max_pixel`` of each chosen map in every image.
+    Returns ``(highest_indices (num_images, num_points, 2), indices (num_points,) int64)``; like the
+    reference's slice, at most ``num_tokens`` points come back.
+    """
+    if maps.dim() != 4:
+        raise ValueError(f"maps must be (num_images, num_tokens, h, w), got {tuple(maps.shape)}")
+    M, N, h, w = maps.shape
+    k = max(0, min(int(num_points), N))
+    entropy = _sum_in_order(ops.entropy_keys_batch(maps))
+    indices = _rank_ascending(entropy, k)
+    chosen = maps[:, indices].contiguous()
+    highest = find_max_pixel(chosen.view(M * k, h, w)) if k else maps.new_zeros(0, 2)
+    return highest.reshape(M, k, 2), indices
+
+
+Correspondences = collections.namedtuple("Correspondences", ["indices", "points", "entropy", "image_entropy"])
+
+
+@torch.no_grad()
+def correspond_images(ldm, images, context, num_points=10, candidates=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
+                      noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
+                      augmentation_iterations=20, controllers=None, upscale_size=128, entropy_scale=1.0,
+                      image_batch=None):
+    """Which tokens of ``context`` are jointly sharp on these unlabelled images, and where (extra:
+    ``find_corresponding_points``, eval.py:159-195, on the TTA averages of eval.py:327-355, without
+    the averages in memory).
+
+    ``images`` is (M, 3, H, W) in [0, 1].  The thetas are drawn as ``predict_keypoints`` draws them
+    (image 0's ``augmentation_iterations`` draws, then image 1's, …), every pass of whole images'
+    copies is captured by ``run_and_find_attn_per_image`` for the ``candidates`` (token ids; default
+    every token of ``context``) at ``upscale_size`` and reduced by ``ops.tta_reduce_entropy``: the
+    argmax of each candidate's average and the entropy of ``softmax(entropy_scale · average)`` in
+    one pass.  Images per pass: what ``AUG_BATCH_PIXELS`` allows and what keeps the captured maps
+    below 2^31 elements, or ``image_batch``.  The entropies are summed over the images image by
+    image, in order, and ranked ascending (ties by position among the candidates, NaN last).
+
+    Returns ``Correspondences(indices, points, entropy, image_entropy)``: ``indices`` (k,) int64 the
+    ids of the k = min(``num_points``, candidates) tokens with the lowest summed entropy, ``points``
+    (M, k, 2) their (row, col) = position / ``upscale_size`` in every image, ``entropy`` (n_cand,)
+    float64 the sums and ``image_entropy`` (M, n_cand) float64, both in candidate order.  Single
+    process only: under a process group of more than one rank it raises.
+    """
+    from .optimize import _world
+    if _world()[0] > 1:
+        raise ValueError("correspond_images runs in a single process (world size must be 1)")
+    imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
+    if imgs.dim() == 3:
+        imgs = imgs[None]
+    if imgs.dim() != 4 or imgs.shape[1] != 3:
+        raise ValueError(f"images must be (M, 3, H, W) or (3, H, W), got {tuple(imgs.shape)}")
+    imgs = imgs.to(device, torch.float32)
+    M, C, S = imgs.shape[0], int(augmentation_iterations), int(upscale_size)
+    if M < 1:
+        raise ValueError("at least one image is needed")
+    if C < 1:
+        raise ValueError("augmentation_iterations must be at least 1")
+    if S < 2:
+        raise ValueError("upscale_size must be at least 2")
+    if candidates is None:
+        candidates = torch.arange(context.shape[-2])
+    candidates = torch.as_tensor(candidates, dtype=torch.int64).reshape(-1).cpu()
+    n = len(candidates)
+    if n < 1:
+        raise ValueError("at least one candidate token is needed")
+    if C * n * S * S >= 2 ** 31:
+        raise ValueError(f"one image's captured maps ({C} x {n} x {S} x {S}) reach 2^31 elements: rank fewer "
+                         "candidates at a time or lower upscale_size")
+    k = max(0, min(int(num_points), n))
+    T = RandomAffineWithInverse(degrees=augment_degrees, scale=augment_scale, translate=augment_translate)
+    theta = torch.cat([T.draw_theta(1) for _ in range(M * C)]).reshape(M, C, 2, 3)
+    if image_batch is None:
+        image_batch = min(AUG_BATCH_PIXELS // (imgs.shape[-1] * imgs.shape[-2] * C), (2 ** 31 - 1) // (C * n * S * S))
+    per_pass = max(1, int(image_batch))
+    pos, ents = [], []
+    for i0 in range(0, M, per_pass):
+        nb = min(per_pass, M - i0)
+        aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
+        with _reproducible_convolutions():
+            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
+                                                        layers=layers, upsample_res=S, indices=candidates,
+                                                        controllers=controllers)
+        maps = torch.stack([per[c][b] for b in range(nb * C) for c in range(len(per))])
+        if tuple(maps.shape) != (nb * C, n, S, S):
+            raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
+        th_inv = T.theta_inverse().reshape(nb, C, 2, 3).to(device)
+        p, e, _ = ops.tta_reduce_entropy(maps.reshape(nb, C, n, S, S), th_inv, scale=entropy_scale)
+        del maps, per
+        pos.append(p)
+        ents.append(e)
+    image_entropy = torch.cat(ents)
+    entropy = _sum_in_order(image_entropy)
+    order = _rank_ascending(entropy, k)
+    points = torch.cat(pos)[:, order] / S
+    return Correspondences(candidates.to(order.device)[order], points, entropy, image_entropy)

@@ -7,7 +7,12 @@ optimize (``optimize_embedding`` → ``embedding.pt``) → find_indices (``find_
 (extra) instead writes the keypoints of the dataset's images — the stage for unlabelled ``custom``
 folders — from ``embedding.pt`` and ``indices.pt`` (``keypoints.pt``, ``keypoints.csv``, and
 ``regressed_keypoints.pt`` when ``regressor.pt`` is there; with ``--num_subjects k`` > 1 also the k peaks per token,
-``subject_keypoints.pt``, ``subject_peak_values.pt`` and ``subject_keypoints.csv``) and stops, in one process.  With ``--visualize``,
+``subject_keypoints.pt``, ``subject_peak_values.pt`` and ``subject_keypoints.csv``) and stops, in one process.  With
+``--correspond`` the stage needs no ``indices.pt``: it first picks the ``--top_k`` tokens of the embedding that are jointly
+sharpest on the dataset's own images (``eval.correspond_images``: lowest summed softmax entropy of the TTA averages at
+``--correspond_size``, scaled by ``--entropy_scale``), writes ``correspondence_indices.pt`` (k,),
+``correspondence_entropy.pt`` (N,) and ``correspondence_points.pt`` (M, k, 2) (with ``--visualize`` also
+``correspondences.png``), and predicts with those tokens; ``regressor.pt`` is then ignored.  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -79,6 +84,15 @@ def build_parser():
                    help="predict stage only: also write keypoint_scores.pt (M, n, 3) = peak, concentration and "
                         "coverage per keypoint, refined_keypoints.pt (M, n, 2), the sub-pixel centroid around each "
                         "peak, and keypoint_scores.csv")
+    p.add_argument("--correspond", action="store_true",
+                   help="predict stage only: instead of reading indices.pt, pick the --top_k tokens of embedding.pt with "
+                        "the lowest softmax entropy of their TTA averages, summed over the dataset's images "
+                        "(correspondence_indices.pt, correspondence_entropy.pt, correspondence_points.pt), and "
+                        "predict with them")
+    p.add_argument("--correspond_size", type=int, default=128,
+                   help="--correspond: side of the TTA averages the entropies are taken on")
+    p.add_argument("--entropy_scale", type=float, default=1.0,
+                   help="--correspond: the averages are multiplied by this before the softmax")
     return p
 
 
@@ -108,6 +122,40 @@ def _image_names(dataset):
     return None if names is None else list(names)
 
 
+def correspond_stage(args, ldm, controllers, embedding, dataset):
+    """``--correspond``: ``eval.correspond_images`` over every image of ``dataset`` for ``--top_k`` of the
+    embedding's tokens.  Writes ``correspondence_indices.pt`` (k,) int64, ``correspondence_entropy.pt``
+    (N,) float64 (per token, summed over the images) and ``correspondence_points.pt`` (M, k, 2), and with
+    ``--visualize`` ``correspondences.png``: the first 12 images at most in one row with their k points,
+    keypoint j in colour j in every image.  The CPU and device RNG states are what they were on entry
+    when it returns, so the prediction that follows draws what a plain predict run draws.  Returns
+    the indices."""
+    from . import ops
+    from .eval import correspond_images
+    from .visualize import save_png
+    folder = args.save_folder
+    cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state(args.device)
+    images = torch.stack([torch.as_tensor(dataset[i]["img"]) for i in range(len(dataset))])
+    corr = correspond_images(ldm, images, embedding, num_points=args.top_k, device=args.device, layers=args.layers,
+                             noise_level=args.noise_level, augment_degrees=args.augment_degrees,
+                             augment_scale=args.augment_scale, augment_translate=args.augment_translate,
+                             augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                             upscale_size=args.correspond_size, entropy_scale=args.entropy_scale)
+    torch.save(corr.indices.cpu(), os.path.join(folder, "correspondence_indices.pt"))
+    torch.save(corr.entropy.cpu(), os.path.join(folder, "correspondence_entropy.pt"))
+    torch.save(corr.points.cpu(), os.path.join(folder, "correspondence_points.pt"))
+    if args.visualize:
+        m = min(12, images.shape[0])
+        f = 2 if images.shape[-1] % 2 == 0 and images.shape[-2] % 2 == 0 else 1
+        sheet = ops.render_sheet(images[:m].to(args.device, torch.float32), None, corr.points[:m], rows=1, cols=m,
+                                 downscale=f)
+        save_png(sheet, os.path.join(folder, "correspondences.png"))
+    print("correspond: indices", corr.indices.tolist(), flush=True)
+    torch.set_rng_state(cpu_state)
+    torch.cuda.set_rng_state(dev_state, args.device)
+    return corr.indices
+
+
 def predict_stage(args, ldm, controllers, batch=4):
     """``--start_from_stage predict``: the keypoints of every image of the dataset (built as
     ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
@@ -121,16 +169,25 @@ def predict_stage(args, ldm, controllers, batch=4):
     ``find_k_max_pixels`` on the TTA average / 512 (round 0 is ``keypoints.pt``'s argmax),
     ``subject_peak_values.pt`` (M, n, k), the value that won each round, and ``subject_keypoints.csv``
     (no header: index, file name where the reader has one, then per token and round row, col, value).
-    Round j of two tokens need not belong to the same instance; the regressor sees round 0 only."""
+    Round j of two tokens need not belong to the same instance; the regressor sees round 0 only.
+    With ``--correspond`` the indices come from ``correspond_stage`` on the same images, not from
+    ``indices.pt``, and ``regressor.pt`` is not applied (it was fitted to other tokens)."""
     import csv
     from .datasets import make_dataset
     from .eval import predict_keypoints
     folder = args.save_folder
     embedding = _load(folder, "embedding.pt", args.device).detach()
-    indices = _load(folder, "indices.pt", args.device).detach()
-    regressor = _load(folder, "regressor.pt", args.device) if os.path.exists(os.path.join(folder, "regressor.pt")) else None
     dataset = make_dataset(args.dataset_name, args.dataset_loc, max_len=args.max_len, validation=args.validation,
                            split="test")
+    have_regressor = os.path.exists(os.path.join(folder, "regressor.pt"))
+    if args.correspond:
+        indices = correspond_stage(args, ldm, controllers, embedding, dataset)
+        if have_regressor:
+            print("predict: --correspond ignores regressor.pt (it was fitted to other tokens)", flush=True)
+        regressor = None
+    else:
+        indices = _load(folder, "indices.pt", args.device).detach()
+        regressor = _load(folder, "regressor.pt", args.device) if have_regressor else None
     names = _image_names(dataset)
     k = int(args.num_subjects)
     kps, regs, scos, refs, pks, vals = [], [], [], [], [], []
@@ -206,6 +263,12 @@ def main(argv=None):
         if args.num_subjects > 1 and args.keypoint_scores:
             parser.error("--start_from_stage predict: --num_subjects > 1 and --keypoint_scores each need their own "
                          "TTA reduce; run the stage once with each")
+    if args.correspond and args.start_from_stage != "predict":
+        parser.error("--correspond belongs to --start_from_stage predict")
+    if not 0.0 < args.entropy_scale < float("inf"):
+        parser.error("--entropy_scale must be positive and finite")
+    if args.correspond_size < 2:
+        parser.error("--correspond_size must be at least 2")
     from .launch import launcher_env, spawn_ranks
     # torch.cuda.device_count() does not initialise HIP on this image, so the ranks can still start
     n = ranks_to_start(args, torch.cuda.device_count(), launcher_env())

@@ -2249,3 +2249,34 @@ def tta_reduce_peaks(maps, theta_inv, num, radius=None, return_avg=False):
         call("skp_tta_reduce_peaks", ptr(maps), B, C, n, S, ptr(th), num, radius2, ptr(pos), ptr(values), ptr(avg),
              ptr(ws), stream(dev))
     return pos, values, avg
+
+
+def tta_reduce_entropy_bytes(B, C, n, S, avg=False):
+    """Byte model of skp_tta_reduce_entropy: ``tta_reduce_bytes`` plus the entropy partials, two
+    doubles per image, token and 64 × 4-pixel tile, written once and read once."""
+    tiles = ((S + 63) // 64) * ((S + 3) // 4)
+    return tta_reduce_bytes(B, C, n, S, avg) + 32 * B * n * tiles
+
+
+def tta_reduce_entropy(maps, theta_inv, scale=1.0, return_avg=False):
+    """``tta_reduce`` with the softmax entropy of every averaged plane (skp_tta_reduce_entropy;
+    eval.py:327-355, then the key of eval.find_corresponding_points, eval.py:159-195).
+
+    Returns ``(pos, entropy, avg)``: ``pos`` and ``avg`` are ``tta_reduce``'s, bit for bit;
+    ``entropy`` (B, n) float64 is the Shannon entropy of ``softmax(scale · a)`` over the S² pixels
+    of each average ``a``, reduced in one pass (log S0 − T / S0 about the maximum, in double, fixed
+    orders).  A plane whose maximum is +inf gives NaN.  The average is not in memory unless
+    ``return_avg``.  ``scale`` must be positive and finite.
+    """
+    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_entropy", maps, theta_inv)
+    scale = float(scale)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"tta_reduce_entropy: scale must be positive and finite, got {scale}")
+    ws = _tta_workspace("tta_reduce_entropy", dev, B, n, S)
+    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
+    entropy = torch.empty(B, n, device=dev, dtype=torch.float64)
+    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
+    with _timed("skp_tta_reduce_entropy", tta_reduce_entropy_bytes(B, C, n, S, return_avg)):
+        call("skp_tta_reduce_entropy", ptr(maps), B, C, n, S, ptr(th), scale, ptr(pos), ptr(entropy), ptr(avg),
+             ptr(ws), stream(dev))
+    return pos, entropy, avg

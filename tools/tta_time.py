@@ -1,6 +1,6 @@
-"""Dev probe: the three TTA reduces at the TTA job sizes, one subcommand each.
+"""Dev probe: the TTA reduces at the TTA job sizes, one subcommand each.
 
-Shapes (B, C, n, S) = (1, 10, 10, 512) and (4, 10, 10, 512).  Each row is the median of ``--iters``
+Shapes (B, C, n, S) = (1, 10, 10, 512) and (4, 10, 10, 512); ``entropy`` takes the selection's shapes.  Each row is the median of ``--iters``
 after ``--warmup``, the launches between two HIP events, in one process.
 
 ``reduce``: skp_tta_reduce with and without the average written, against the byte model and against
@@ -19,6 +19,10 @@ written by (a) or (b):
       num (the summed warps of a plane of ones) gathered at the peak.  peaks:
       ops.tta_reduce(return_avg=True), then ops.find_k_max_pixels on the average (the positions
       only; whether (b)'s positions equal them is recorded beside the times).
+``entropy`` (scale 1) at (1, 10, 500, 128), (4, 10, 500, 128) (a whole embedding at the selection's
+size) and (1, 10, 10, 512), the same scheme: (b) skp_tta_reduce_entropy, (c) ops.tta_reduce(
+return_avg=True) then ops.entropy_keys_batch on the average (the entropy of the reference's fp32
+arithmetic; how far (b)'s double one-pass entropy is from it is recorded beside the times).
 (a) is timed twice, before and after (b): the difference of its two medians is the run-to-run
 spread that (b) − (a), and (b) against (c), are read with.
 
@@ -26,7 +30,7 @@ Kernel times of ``scored`` and ``peaks`` come from a run of their own: under ``r
 --kernel-trace`` with ``--trace-only`` the subcommand only launches (a) and (b) a few times per
 shape (and num), and ``--kernel-trace FILE.csv`` folds that trace's per-kernel medians into the
 result.
-Usage: python tools/tta_time.py {reduce,scored,peaks} [--out FILE.json] [--kernel-trace kernel_trace.csv]
+Usage: python tools/tta_time.py {reduce,scored,peaks,entropy} [--out FILE.json] [--kernel-trace kernel_trace.csv]
        rocprofv3 --kernel-trace -d DIR -o tta --output-format csv -- python tools/tta_time.py scored --trace-only
 """
 import argparse
@@ -48,12 +52,15 @@ DEV = "cuda:0"
 SHAPES = ((1, 10, 10, 512), (4, 10, 10, 512))
 DISTANCE = 5.0
 NUMS = (2, 3)
+ENTROPY_SHAPES = ((1, 10, 500, 128), (4, 10, 500, 128), (1, 10, 10, 512))
 # kernel and template argument -> the name its medians go by in each subcommand's result
 SCORED_KERNELS = {"tta_window_kernel": "window", "tta_merge_kernel<kScored>": "merge_scored",
                   "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<true>": "tile_scored",
                   "tta_tile_kernel<false>": "tile_plain"}
 PEAKS_KERNELS = {"tta_masked_tile_kernel": "tta_masked_tile_kernel", "tta_merge_kernel<kPeaks>": "tta_merge_peaks_kernel",
                  "tta_merge_kernel<kPlain>": "tta_merge_kernel", "tta_tile_kernel<false>": "tta_tile_kernel"}
+ENTROPY_KERNELS = {"tta_tile_entropy_kernel": "tile_entropy", "tta_merge_kernel<kEntropy>": "merge_entropy",
+                   "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<false>": "tile_plain"}
 
 
 def median_us(f, warmup, iters):
@@ -81,13 +88,13 @@ def record(a, rows, name, f, nbytes, floor=False):
     return med
 
 
-def cases():
+def cases(shapes=SHAPES):
     """Per shape: the shape, random maps, the inverse thetas of seeded random affines, and the plain
     reduce's workspace and position buffer."""
     torch.manual_seed(0)
     from stablekeypoints_amd.invertable_transform import RandomAffineWithInverse
     T = RandomAffineWithInverse(degrees=30, scale=(0.9, 1.1), translate=(0.1, 0.1))
-    for B, C, n, S in SHAPES:
+    for B, C, n, S in shapes:
         maps = torch.rand(B, C, n, S, S, device=DEV)
         T.last_params = {"theta": T.draw_theta(B * C)}
         theta = T.theta_inverse().reshape(B, C, 2, 3).to(DEV)
@@ -102,14 +109,14 @@ def kernel_medians(path, names):
         for row in csv.DictReader(fh):
             name = row["Kernel_Name"]
             kernel = next((k for k in ("tta_window_kernel", "tta_masked_tile_kernel", "tta_merge_kernel",
-                                       "tta_tile_kernel") if k in name), None)
+                                       "tta_tile_kernel", "tta_tile_entropy_kernel") if k in name), None)
             if kernel == "tta_tile_kernel":     # the template argument, demangled or mangled
                 kernel += "<true>" if ("<true>" in name or "ILb1" in name) else "<false>"
             elif kernel == "tta_merge_kernel":
-                kernel += "<" + ("kPlain", "kScored", "kPeaks")[int(re.search(r"Variant\)?E?([012])", name).group(1))] + ">"
+                kernel += "<" + ("kPlain", "kScored", "kPeaks", "kEntropy")[int(re.search(r"Variant\)?E?([0123])", name).group(1))] + ">"
             if kernel not in names:
                 continue
-            grid = "x".join(str(row.get(f"Grid_Size_{d}", "?")) for d in "XY")
+            grid = "x".join(str(row.get(f"Grid_Size_{d}", "?")) for d in ("XYZ" if "entropy" in kernel else "XY"))
             by.setdefault(f"{names[kernel]}_grid{grid}", []).append(
                 (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
     return {k: dict(median_us=round(statistics.median(v), 2), launches=len(v)) for k, v in sorted(by.items())}
@@ -293,10 +300,57 @@ def run_peaks(a):
                   summary=summary, rows=rows), PEAKS_KERNELS)
 
 
+# ------------------------------------------------------------------------------------------ entropy
+def entropy_composition(maps, theta):
+    """The outputs of tta_reduce_entropy from the ops that exist without it: the average written, then
+    its softmax entropies (four passes over it)."""
+    pos, avg = ops.tta_reduce(maps, theta, return_avg=True)
+    return pos, ops.entropy_keys_batch(avg)
+
+
+def run_entropy(a):
+    rows, summary = [], []
+    for (B, C, n, S), maps, theta, ws, pos in cases(ENTROPY_SHAPES):
+        wse = torch.empty(lib().skp_tta_reduce_entropy_workspace(B, n, S) // 8, device=DEV, dtype=torch.int64)
+        ent = torch.empty(B, n, device=DEV, dtype=torch.float64)
+
+        def plain():
+            call("skp_tta_reduce", ptr(maps), B, C, n, S, ptr(theta), ptr(pos), None, ptr(ws), stream(DEV))
+
+        def entropy():
+            call("skp_tta_reduce_entropy", ptr(maps), B, C, n, S, ptr(theta), 1.0, ptr(pos), ptr(ent), None, ptr(wse),
+                 stream(DEV))
+
+        if a.trace_only:
+            trace(plain, entropy)
+            continue
+        # (c) moves the fused reduce with the average written, then reads the average four times
+        comp_bytes = ops.tta_reduce_bytes(B, C, n, S, True) + 4 * B * n * S * S * 4
+        a_, spread, b_, c_ = a_b_a_c(a, rows, f"B{B}_C{C}_n{n}_S{S}", "skp_tta_reduce_entropy", plain, entropy,
+                                     lambda: entropy_composition(maps, theta), ops.tta_reduce_bytes(B, C, n, S),
+                                     ops.tta_reduce_entropy_bytes(B, C, n, S), comp_bytes)
+        got_pos, got_ent, _ = ops.tta_reduce_entropy(maps, theta)
+        want_pos, want_ent = entropy_composition(maps, theta)
+        summary.append(dict(shape=[B, C, n, S], a_us=round(a_, 2), a_spread_us=round(spread, 2), b_us=round(b_, 2),
+                            c_us=round(c_, 2), b_minus_a_us=round(b_ - a_, 2), b_over_c=round(b_ / c_, 3),
+                            b_below_c_by_more_than_spread=bool(b_ < c_ - spread),
+                            pos_agree=bool(torch.equal(got_pos, want_pos)),
+                            entropy_max_abs_vs_fp32_order=float((got_ent - want_ent).abs().max())))
+        print(json.dumps(summary[-1]), flush=True)
+    if a.trace_only:
+        return
+    write(a, dict(device=torch.cuda.get_device_name(0), warmup=a.warmup, iters=a.iters, scale=1.0,
+                  note="median of iters, launches between two HIP events; a = skp_tta_reduce (the lower of two medians, "
+                       "their difference = a_spread), b = skp_tta_reduce_entropy, c = the composition ops.tta_reduce("
+                       "return_avg=True) + ops.entropy_keys_batch (host time between its launches included); no average "
+                       "written by a or b; kernels = per-kernel medians of a kernel trace taken in a run of its own",
+                  summary=summary, rows=rows), ENTROPY_KERNELS)
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="which", required=True)
-    for name, run in (("reduce", run_reduce), ("scored", run_scored), ("peaks", run_peaks)):
+    for name, run in (("reduce", run_reduce), ("scored", run_scored), ("peaks", run_peaks), ("entropy", run_entropy)):
         p = sub.add_parser(name)
         p.set_defaults(run=run)
         p.add_argument("--out", default=None)
