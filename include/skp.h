@@ -141,13 +141,15 @@ int skp_gaussian_target(const float* pos, int num, int T, int size, float sigma,
 /* ---------------------------------------------------------------- A8-A10 select
  * ptp_utils.find_top_k_gaussian (ptp_utils.py:86-112): per-token
  * KL(normalised G(argmax)+eps ‖ softmax(map+eps)), ascending, first top_k
- * (ties by token id).  kl (T) doubles optional; workspace >= 16*T bytes.       */
+ * (ties by token id).  kl (T) doubles optional; workspace >= 8*T bytes, 8-B aligned: it
+ * holds the keys when kl is NULL and is not touched otherwise (it may then be kl itself). */
 int skp_topk_gaussian(const float* maps, int T, int h, int w, int top_k, float sigma, float epsilon,
                       int num_subjects, long long* out, double* kl, void* workspace, void* stream);
 
 /* skp_topk_gaussian for nb images in one launch (each image's top-k chosen as the reference's
  * find_top_k_gaussian on that image, ptp_utils.py:86-112; optimize.py:403-410 per replica):
- * maps (nb, T, h, w), out (nb, top_k), kl (nb, T) optional, workspace >= 16*nb*T bytes.      */
+ * maps (nb, T, h, w), out (nb, top_k), kl (nb, T) optional, workspace >= 8*nb*T bytes (as
+ * skp_topk_gaussian's: the keys when kl is NULL).                                            */
 int skp_topk_gaussian_batch(const float* maps, int nb, int T, int h, int w, int top_k, float sigma,
                             float epsilon, int num_subjects, long long* out, double* kl, void* workspace,
                             void* stream);
@@ -158,14 +160,18 @@ int skp_topk_gaussian_batch(const float* maps, int nb, int T, int h, int w, int 
  * together are skp_topk_gaussian_batch with top_k > 0.                                        */
 int skp_topk_keys(const double* keys, int nb, int T, int top_k, long long* out, void* stream);
 
-/* ptp_utils.entropy_sort (ptp_utils.py:165-187): ascending softmax entropy.     */
+/* ptp_utils.entropy_sort (ptp_utils.py:165-187): ascending softmax entropy.  ent (T)
+ * doubles optional; workspace >= 8*T bytes, 8-B aligned (the keys when ent is NULL,
+ * not touched otherwise); out is not written when top_k == 0.                   */
 int skp_entropy_sort(const float* maps, int T, int h, int w, int top_k, long long* out, double* ent,
                      void* workspace, void* stream);
 
 /* ptp_utils.furthest_point_sampling (ptp_utils.py:115-159) on the argmax positions
  * of the candidate rows; strict '>' first-wins, IEEE sqrt distances.
- * out[top_k] (int64); n_out (device int) = how many were selected.
- * workspace >= 16 * n_cand bytes.                                              */
+ * out[top_k] (int64); n_out (device int, optional) = how many were selected;
+ * out[n_out:] = -1 (every entry of out is written).
+ * workspace >= 8 * n_cand bytes (skp_fps_batch's with nb = 1: the candidates'
+ * argmax positions, two floats each), 4-B aligned.                             */
 int skp_fps(const float* maps, int T, int h, int w, const long long* cand, int n_cand, int top_k,
             long long* out, int* n_out, void* workspace, void* stream);
 /* skp_fps for nb images in one launch (ptp_utils.py:115-159 per replica, optimize.py:419-424):

@@ -721,7 +721,7 @@ def furthest_point_sampling_batch(maps, top_k, candidates):
         raise ValueError(f"candidates {tuple(cand.shape)} for {nb} images")
     out = torch.empty(nb, top_k, device=maps.device, dtype=torch.int64)
     n_out = torch.empty(nb, device=maps.device, dtype=torch.int32)
-    ws = torch.empty(2 * cand.numel() + 2, device=maps.device, dtype=F32)
+    ws = torch.empty(2 * cand.numel(), device=maps.device, dtype=F32)
     call("skp_fps_batch", ptr(maps), nb, T, h, w, ptr(cand), cand.shape[1], int(top_k), ptr(out), ptr(n_out),
          ptr(ws), stream(maps.device))
     return out, n_out
@@ -743,7 +743,7 @@ def fps_from_keys_batch(keys, maps, n_cand, top_k):
     cand = torch.empty(nb, n_cand, device=dev, dtype=torch.int64)
     out = torch.empty(nb, top_k, device=dev, dtype=torch.int64)
     n_out = torch.empty(nb, device=dev, dtype=torch.int32)
-    ws = torch.empty(2 * nb * n_cand + 2, device=dev, dtype=F32)
+    ws = torch.empty(2 * nb * n_cand, device=dev, dtype=F32)
     call("skp_fps_keys_batch", ptr(keys), ptr(maps), nb, T, h, w, n_cand, int(top_k), ptr(cand), ptr(out), ptr(n_out),
          ptr(ws), stream(dev))
     return out, n_out, cand
@@ -817,7 +817,7 @@ def furthest_point_sampling(maps, top_k, candidates):
     cand = candidates.to(device=maps.device, dtype=torch.int64).contiguous()
     out = torch.empty(top_k, device=maps.device, dtype=torch.int64)
     n_out = torch.empty(1, device=maps.device, dtype=torch.int32)
-    ws = torch.empty(2 * cand.numel() + 2, device=maps.device, dtype=F32)
+    ws = torch.empty(2 * cand.numel(), device=maps.device, dtype=F32)
     call("skp_fps", ptr(maps), T, h, w, ptr(cand), cand.numel(), int(top_k), ptr(out), ptr(n_out), ptr(ws),
          stream(maps.device))
     return out, n_out
