@@ -557,6 +557,36 @@ int skp_tta_reduce_entropy_workspace(int B, int n, int S);
 int skp_tta_reduce_entropy(const float* maps, int B, int C, int n, int S, const float* theta_inv, float scale,
                            float* pos, double* entropy, float* avg, void* workspace, void* stream);
 
+/* The part TTA reduce: skp_tta_reduce (eval.py:327-355, then eval.find_max_pixel, eval.py:39-60)
+ * and, in the same pass and without the average in memory, the reduction over the TOKEN axis at
+ * every pixel: which token holds the greatest average there, that average, and the tokens' sum.
+ *   pos, avg: skp_tta_reduce's, bit for bit.  label (B, S, S) int16, value (B, S, S), mass (B, S, S).
+ *   With a[b,t,p] the fp32 average of image b, token t and pixel p (after NaN -> 0):
+ *   value[b,p] = max_t a[b,t,p];
+ *   label[b,p] = the lowest t with a[b,t,p] == value[b,p]: a strict > walking t = 0 … n−1 (a holds
+ *                no NaN, so this is a total order; ±inf are ordinary values);
+ *   mass[b,p]  = Σ_t a[b,t,p] in this order: chunk k holds tokens 10k … min(10k + 9, n−1); each
+ *                chunk's sum starts from 0.0f and adds in token order; the chunks' sums are added in
+ *                chunk order, again from 0.0f; every add rounded on its own.  For n <= 10 this is
+ *                the plain sequential sum.  The order is what lets the chunks run in different
+ *                workgroups and give the same bits.
+ * No background decision is made here: a pixel that no copy covers has a = 0 for every token and
+ * gets label 0, value 0, mass 0.
+ * Two or three launches, no atomics: the tile kernel (grid tiles × B × chunks of 10 tokens) leaves
+ * skp_tta_reduce's partials, and each thread carries its pixel's (value, label, mass) through its
+ * chunk's passes; with one chunk it stores the three outputs, with more it stores a partial per
+ * image, chunk and pixel, and a per-pixel merge walks the chunks in order (strict >, the earlier
+ * chunk keeps a tie); then the merge for pos.  Deterministic, and the same whether or not avg is
+ * asked for.
+ * workspace: skp_tta_reduce_parts_workspace(B, n, S) bytes (−1 on a bad shape or at 2^31 bytes),
+ * 8-B aligned: skp_tta_reduce's partials and, with chunks = ⌈n / 10⌉ > 1 and Q = B·chunks·S², two
+ * floats and an int16 per partial, each array rounded up to 8 bytes: 8·B·n·T + 2·r8(4Q) + r8(2Q).
+ * Rejected before any launch: what skp_tta_reduce rejects, a null label, value or mass, n > 32767,
+ * more than 65535 chunks.                                                                      */
+int skp_tta_reduce_parts_workspace(int B, int n, int S);
+int skp_tta_reduce_parts(const float* maps, int B, int C, int n, int S, const float* theta_inv, float* pos,
+                         short* label, float* value, float* mass, float* avg, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

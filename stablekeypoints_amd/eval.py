@@ -13,6 +13,9 @@ captures and the whole TTA reduce (inverse warps, sums, ratio, argmax) in one ke
 ``find_corresponding_points`` (``:159-195``) picks the tokens whose maps are jointly sharpest on a
 set of images; ``correspond_images`` (extra) does so on the TTA averages of unlabelled images, with
 each average's argmax and softmax entropy from ``skp_tta_reduce_entropy``.
+``part_maps`` (extra) says which of the chosen tokens owns each pixel of unlabelled images: per pixel
+the greatest of the tokens' TTA averages, the token that attains it and the tokens' sum from
+``skp_tta_reduce_parts``; ``foreground_iou`` scores the labelled pixels against a foreground mask.
 """
 import collections
 import contextlib
@@ -469,3 +472,112 @@ def correspond_images(ldm, images, context, num_points=10, candidates=None, devi
     order = _rank_ascending(entropy, k)
     points = torch.cat(pos)[:, order] / S
     return Correspondences(candidates.to(order.device)[order], points, entropy, image_entropy)
+
+
+PartMaps = collections.namedtuple("PartMaps", ["label", "value", "mass", "points", "area"])
+
+
+@torch.no_grad()
+def part_maps(ldm, images, context, indices=None, device="cuda", layers=(0, 1, 2, 3, 4, 5), noise_level=-1,
+              augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1), augmentation_iterations=20,
+              controllers=None, upscale_size=128, part_threshold=0.0, image_batch=None):
+    """Which of the chosen tokens owns each pixel of these unlabelled images (extra: the unsupervised
+    part label; the captured maps are a softmax over the tokens at every pixel, so at a pixel the
+    tokens' TTA averages of eval.py:327-355 are comparable), without the averages in memory.
+
+    ``images`` is (M, 3, H, W) in [0, 1].  The thetas are drawn as ``predict_keypoints`` draws them
+    (image 0's ``augmentation_iterations`` draws, then image 1's, …), every pass of whole images'
+    copies is captured by ``run_and_find_attn_per_image`` for ``indices`` (token ids; default every
+    token of ``context``) at ``upscale_size`` and reduced by one ``ops.tta_reduce_parts``: each
+    token's argmax and, per pixel, the greatest average, the lowest token that attains it and the
+    tokens' sum.  Images per pass: what ``AUG_BATCH_PIXELS`` allows and what keeps the captured maps
+    below 2^31 elements, or ``image_batch``.
+
+    Returns ``PartMaps(label, value, mass, points, area)``: ``label`` (M, S, S) int16 the position
+    among ``indices`` of the token that owns the pixel, −1 (background) where ``mass <=
+    part_threshold`` — with the default exactly the pixels that carry no attention, those that no
+    copy covers among them; ``value`` and ``mass`` (M, S, S) the owner's average and the tokens'
+    sum as the kernel left them; ``points`` (M, n, 2) each token's (row, col) = position /
+    ``upscale_size``, ``predict_keypoints``' keypoints; ``area`` (M, n) int64 the pixels each token
+    owns.  Single process only: under a process group of more than one rank it raises.
+    """
+    from .optimize import _world
+    if _world()[0] > 1:
+        raise ValueError("part_maps runs in a single process (world size must be 1)")
+    imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
+    if imgs.dim() == 3:
+        imgs = imgs[None]
+    if imgs.dim() != 4 or imgs.shape[1] != 3:
+        raise ValueError(f"images must be (M, 3, H, W) or (3, H, W), got {tuple(imgs.shape)}")
+    imgs = imgs.to(device, torch.float32)
+    M, C, S = imgs.shape[0], int(augmentation_iterations), int(upscale_size)
+    if M < 1:
+        raise ValueError("at least one image is needed")
+    if C < 1:
+        raise ValueError("augmentation_iterations must be at least 1")
+    if S < 2:
+        raise ValueError("upscale_size must be at least 2")
+    if indices is None:
+        indices = torch.arange(context.shape[-2])
+    indices = torch.as_tensor(indices, dtype=torch.int64).reshape(-1).cpu()
+    n = len(indices)
+    if n < 1:
+        raise ValueError("at least one token is needed")
+    if n > 32767:
+        raise ValueError(f"at most 32767 tokens can be labelled (the label is int16), got {n}")
+    if C * n * S * S >= 2 ** 31:
+        raise ValueError(f"one image's captured maps ({C} x {n} x {S} x {S}) reach 2^31 elements: label fewer "
+                         "tokens at a time or lower upscale_size")
+    T = RandomAffineWithInverse(degrees=augment_degrees, scale=augment_scale, translate=augment_translate)
+    theta = torch.cat([T.draw_theta(1) for _ in range(M * C)]).reshape(M, C, 2, 3)
+    if image_batch is None:
+        image_batch = min(AUG_BATCH_PIXELS // (imgs.shape[-1] * imgs.shape[-2] * C), (2 ** 31 - 1) // (C * n * S * S))
+    per_pass = max(1, int(image_batch))
+    pos, labels, values, masses = [], [], [], []
+    for i0 in range(0, M, per_pass):
+        nb = min(per_pass, M - i0)
+        aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
+        with _reproducible_convolutions():
+            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
+                                                        layers=layers, upsample_res=S, indices=indices,
+                                                        controllers=controllers)
+        maps = torch.stack([per[c][b] for b in range(nb * C) for c in range(len(per))])
+        if tuple(maps.shape) != (nb * C, n, S, S):
+            raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
+        th_inv = T.theta_inverse().reshape(nb, C, 2, 3).to(device)
+        p, lab, val, mas, _ = ops.tta_reduce_parts(maps.reshape(nb, C, n, S, S), th_inv)
+        del maps, per
+        pos.append(p)
+        labels.append(lab)
+        values.append(val)
+        masses.append(mas)
+    mass = torch.cat(masses)
+    label = torch.cat(labels).masked_fill(mass <= float(part_threshold), -1)
+    # the pixels of each label, the background in column 0 (integer adds: any order gives the same counts)
+    owner = (label.long() + 1).reshape(M, S * S)
+    area = torch.zeros(M, n + 1, device=owner.device, dtype=torch.int64).scatter_add_(1, owner, torch.ones_like(owner))
+    return PartMaps(label, torch.cat(values), mass, torch.cat(pos) / S, area[:, 1:].contiguous())
+
+
+def foreground_iou(label, mask):
+    """Per-image intersection over union of the labelled pixels against a foreground mask.
+
+    ``label`` (M, S, S): a pixel is foreground where ``label >= 0`` (``part_maps``' background is
+    −1).  ``mask`` (M, h, w) or (M, h, w, 1) in [0, 1] (the CUB parts reader's ``mask``), resized to
+    (S, S) by nearest neighbour when its size differs; foreground where ``mask > 0.5``.  Returns
+    (M,) float64 on ``label``'s device: |A ∩ B| / |A ∪ B|, and 1.0 where both are empty.
+    """
+    label = torch.as_tensor(label)
+    mask = torch.as_tensor(mask).to(label.device)
+    if mask.dim() == 4 and mask.shape[-1] == 1:
+        mask = mask[..., 0]
+    if label.dim() != 3 or mask.dim() != 3 or mask.shape[0] != label.shape[0]:
+        raise ValueError(f"label must be (M, S, S) and mask (M, h, w) or (M, h, w, 1), got {tuple(label.shape)} "
+                         f"and {tuple(mask.shape)}")
+    if tuple(mask.shape[1:]) != tuple(label.shape[1:]):
+        mask = torch.nn.functional.interpolate(mask[:, None].to(torch.float32), size=tuple(label.shape[1:]),
+                                               mode="nearest")[:, 0]
+    fg, gt = label >= 0, mask > 0.5
+    inter = (fg & gt).flatten(1).sum(1).to(torch.float64)
+    union = (fg | gt).flatten(1).sum(1).to(torch.float64)
+    return torch.where(union > 0, inter / union.clamp_min(1.0), torch.ones_like(union))

@@ -12,7 +12,10 @@ folders — from ``embedding.pt`` and ``indices.pt`` (``keypoints.pt``, ``keypoi
 sharpest on the dataset's own images (``eval.correspond_images``: lowest summed softmax entropy of the TTA averages at
 ``--correspond_size``, scaled by ``--entropy_scale``), writes ``correspondence_indices.pt`` (k,),
 ``correspondence_entropy.pt`` (N,) and ``correspondence_points.pt`` (M, k, 2) (with ``--visualize`` also
-``correspondences.png``), and predicts with those tokens; ``regressor.pt`` is then ignored.  With ``--visualize``,
+``correspondences.png``), and predicts with those tokens; ``regressor.pt`` is then ignored.  With
+``--part_maps`` it also writes which token owns each pixel of every image (``eval.part_maps`` at ``--part_size``:
+``part_labels.pt`` (M, S, S) int16, −1 = background, ``part_mass.pt``, ``part_area.pt``, ``part_points.pt``, ``part_fg_iou.pt``
+where the dataset has foreground masks, and with ``--visualize`` ``parts.png``).  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -93,6 +96,15 @@ def build_parser():
                    help="--correspond: side of the TTA averages the entropies are taken on")
     p.add_argument("--entropy_scale", type=float, default=1.0,
                    help="--correspond: the averages are multiplied by this before the softmax")
+    p.add_argument("--part_maps", action="store_true",
+                   help="predict stage only: also write which token owns each pixel of every image's TTA averages "
+                        "(part_labels.pt (M, S, S) int16 with -1 = background, part_mass.pt, part_area.pt, "
+                        "part_points.pt, and part_fg_iou.pt where the dataset has foreground masks)")
+    p.add_argument("--part_size", type=int, default=128, help="--part_maps: side S of the part maps")
+    p.add_argument("--part_tokens", type=str, default="indices", choices=["indices", "all"],
+                   help="--part_maps: label with the prediction's tokens, or with every token of embedding.pt")
+    p.add_argument("--part_threshold", type=float, default=0.0,
+                   help="--part_maps: a pixel whose tokens' attention sums to this or less is background")
     return p
 
 
@@ -156,6 +168,56 @@ def correspond_stage(args, ldm, controllers, embedding, dataset):
     return corr.indices
 
 
+def parts_stage(args, ldm, controllers, embedding, indices, dataset):
+    """``--part_maps``: ``eval.part_maps`` over every image of ``dataset`` at ``--part_size``, for the
+    prediction's ``indices`` or (``--part_tokens all``) every token of the embedding.  Writes
+    ``part_labels.pt`` (M, S, S) int16 (the token's position among those tokens, −1 = background: the
+    tokens' attention sums to ``--part_threshold`` or less), ``part_mass.pt`` (M, S, S), ``part_area.pt``
+    (M, n) int64 and ``part_points.pt`` (M, n, 2); where the dataset's items carry ``mask`` also
+    ``part_fg_iou.pt`` (M,) float64, ``eval.foreground_iou`` of the labels against it, and prints its mean.
+    With ``--visualize`` ``parts.png``: the first 12 images at most in one row, every non-background pixel
+    blended with its token's colour (``ops.default_colors``, the labels nearest-upsampled to the image
+    size) and the tokens' points on top, token j in colour j.  The CPU and device RNG states are what they
+    were on entry when it returns, so the prediction that follows draws what a plain predict run draws."""
+    from . import ops
+    from .eval import foreground_iou, part_maps
+    from .visualize import save_png
+    folder = args.save_folder
+    cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state(args.device)
+    items = [dataset[i] for i in range(len(dataset))]
+    images = torch.stack([torch.as_tensor(it["img"]) for it in items])
+    parts = part_maps(ldm, images, embedding, None if args.part_tokens == "all" else indices.cpu(), device=args.device,
+                      layers=args.layers, noise_level=args.noise_level, augment_degrees=args.augment_degrees,
+                      augment_scale=args.augment_scale, augment_translate=args.augment_translate,
+                      augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                      upscale_size=args.part_size, part_threshold=args.part_threshold)
+    torch.save(parts.label.cpu(), os.path.join(folder, "part_labels.pt"))
+    torch.save(parts.mass.cpu(), os.path.join(folder, "part_mass.pt"))
+    torch.save(parts.area.cpu(), os.path.join(folder, "part_area.pt"))
+    torch.save(parts.points.cpu(), os.path.join(folder, "part_points.pt"))
+    if items and all("mask" in it for it in items):
+        masks = torch.stack([torch.as_tensor(it["mask"], dtype=torch.float32) for it in items])
+        iou = foreground_iou(parts.label, masks).cpu()
+        torch.save(iou, os.path.join(folder, "part_fg_iou.pt"))
+        print(f"part_maps: mean foreground IoU {float(iou.mean()):.4f} over {iou.shape[0]} images", flush=True)
+    if args.visualize:
+        m = min(12, images.shape[0])
+        H, W = images.shape[-2:]
+        n = parts.points.shape[1]
+        shown = images[:m].to(args.device, torch.float32)
+        label = torch.nn.functional.interpolate(parts.label[:m, None].float(), size=(H, W), mode="nearest")[:, 0].long()
+        colors = ops.default_colors(n).to(args.device)
+        tint = (colors.float() / 255.0)[label.clamp_min(0)].permute(0, 3, 1, 2)
+        shown = torch.where((label >= 0)[:, None], 0.5 * shown + 0.5 * tint, shown)
+        f = 2 if W % 2 == 0 and H % 2 == 0 else 1
+        sheet = ops.render_sheet(shown, None, parts.points[:m], rows=1, cols=m, downscale=f)
+        save_png(sheet, os.path.join(folder, "parts.png"))
+    print(f"part_maps: {images.shape[0]} images, {parts.points.shape[1]} tokens at {args.part_size} -> "
+          f"{os.path.join(folder, 'part_labels.pt')}", flush=True)
+    torch.set_rng_state(cpu_state)
+    torch.cuda.set_rng_state(dev_state, args.device)
+
+
 def predict_stage(args, ldm, controllers, batch=4):
     """``--start_from_stage predict``: the keypoints of every image of the dataset (built as
     ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
@@ -171,7 +233,9 @@ def predict_stage(args, ldm, controllers, batch=4):
     (no header: index, file name where the reader has one, then per token and round row, col, value).
     Round j of two tokens need not belong to the same instance; the regressor sees round 0 only.
     With ``--correspond`` the indices come from ``correspond_stage`` on the same images, not from
-    ``indices.pt``, and ``regressor.pt`` is not applied (it was fitted to other tokens)."""
+    ``indices.pt``, and ``regressor.pt`` is not applied (it was fitted to other tokens).
+    With ``--part_maps`` ``parts_stage`` first writes the part maps of the same images; the keypoints are
+    the same bits with and without it."""
     import csv
     from .datasets import make_dataset
     from .eval import predict_keypoints
@@ -188,6 +252,8 @@ def predict_stage(args, ldm, controllers, batch=4):
     else:
         indices = _load(folder, "indices.pt", args.device).detach()
         regressor = _load(folder, "regressor.pt", args.device) if have_regressor else None
+    if args.part_maps:
+        parts_stage(args, ldm, controllers, embedding, indices, dataset)
     names = _image_names(dataset)
     k = int(args.num_subjects)
     kps, regs, scos, refs, pks, vals = [], [], [], [], [], []
@@ -269,6 +335,10 @@ def main(argv=None):
         parser.error("--entropy_scale must be positive and finite")
     if args.correspond_size < 2:
         parser.error("--correspond_size must be at least 2")
+    if args.part_maps and args.start_from_stage != "predict":
+        parser.error("--part_maps belongs to --start_from_stage predict")
+    if args.part_size < 2:
+        parser.error("--part_size must be at least 2")
     from .launch import launcher_env, spawn_ranks
     # torch.cuda.device_count() does not initialise HIP on this image, so the ranks can still start
     n = ranks_to_start(args, torch.cuda.device_count(), launcher_env())

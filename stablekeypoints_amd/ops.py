@@ -2280,3 +2280,38 @@ def tta_reduce_entropy(maps, theta_inv, scale=1.0, return_avg=False):
         call("skp_tta_reduce_entropy", ptr(maps), B, C, n, S, ptr(th), scale, ptr(pos), ptr(entropy), ptr(avg),
              ptr(ws), stream(dev))
     return pos, entropy, avg
+
+
+def tta_reduce_parts_bytes(B, C, n, S, avg=False):
+    """Byte model of skp_tta_reduce_parts: ``tta_reduce_bytes`` plus 10 bytes per image and pixel
+    (a float value, an int16 label, a float mass) and, with more than one chunk of 10 tokens, the
+    same 10 bytes per image, chunk and pixel written once and read once (an upper bound: the merge
+    reads the label of the winning chunk only)."""
+    chunks = (n + 9) // 10
+    return tta_reduce_bytes(B, C, n, S, avg) + 10 * B * S * S + (20 * B * chunks * S * S if chunks > 1 else 0)
+
+
+def tta_reduce_parts(maps, theta_inv, return_avg=False):
+    """``tta_reduce`` with the per-pixel reduction over the tokens (skp_tta_reduce_parts).
+
+    Returns ``(pos, label, value, mass, avg)``: ``pos`` and ``avg`` are ``tta_reduce``'s, bit for
+    bit; at every pixel of every image ``value`` (B, S, S) is the greatest of the n averages,
+    ``label`` (B, S, S) int16 the lowest token that attains it, and ``mass`` (B, S, S) the tokens'
+    sum in a fixed order (chunks of 10 tokens: each chunk's sum from 0 in token order, the chunks'
+    sums from 0 in chunk order; the plain sequential sum for n <= 10).  A pixel that no copy
+    covers has label 0, value 0 and mass 0.  The average is not in memory unless ``return_avg``.
+    ``n <= 32767``.
+    """
+    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_parts", maps, theta_inv)
+    if n > 32767:
+        raise ValueError(f"tta_reduce_parts: at most 32767 tokens (the label is int16), got {n}")
+    ws = _tta_workspace("tta_reduce_parts", dev, B, n, S)
+    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
+    label = torch.empty(B, S, S, device=dev, dtype=torch.int16)
+    value = torch.empty(B, S, S, device=dev, dtype=F32)
+    mass = torch.empty(B, S, S, device=dev, dtype=F32)
+    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
+    with _timed("skp_tta_reduce_parts", tta_reduce_parts_bytes(B, C, n, S, return_avg)):
+        call("skp_tta_reduce_parts", ptr(maps), B, C, n, S, ptr(th), ptr(pos), ptr(label), ptr(value), ptr(mass),
+             ptr(avg), ptr(ws), stream(dev))
+    return pos, label, value, mass, avg

@@ -23,6 +23,11 @@ written by (a) or (b):
 size) and (1, 10, 10, 512), the same scheme: (b) skp_tta_reduce_entropy, (c) ops.tta_reduce(
 return_avg=True) then ops.entropy_keys_batch on the average (the entropy of the reference's fp32
 arithmetic; how far (b)'s double one-pass entropy is from it is recorded beside the times).
+``parts`` at (1, 10, 10, 512), (4, 10, 10, 512), (1, 10, 500, 128) and (4, 10, 500, 128), the same scheme:
+(b) skp_tta_reduce_parts, (c) ops.tta_reduce(return_avg=True), then ``avg.max(dim=1)`` and the sum over the
+tokens chunk by chunk in torch (one reduction over each chunk's 10 tokens, one over the chunks); whether
+(b)'s labels, values and positions equal (c)'s, and how far its mass is from (c)'s, is recorded beside the
+times.
 (a) is timed twice, before and after (b): the difference of its two medians is the run-to-run
 spread that (b) − (a), and (b) against (c), are read with.
 
@@ -30,7 +35,7 @@ Kernel times of ``scored`` and ``peaks`` come from a run of their own: under ``r
 --kernel-trace`` with ``--trace-only`` the subcommand only launches (a) and (b) a few times per
 shape (and num), and ``--kernel-trace FILE.csv`` folds that trace's per-kernel medians into the
 result.
-Usage: python tools/tta_time.py {reduce,scored,peaks,entropy} [--out FILE.json] [--kernel-trace kernel_trace.csv]
+Usage: python tools/tta_time.py {reduce,scored,peaks,entropy,parts} [--out FILE.json] [--kernel-trace kernel_trace.csv]
        rocprofv3 --kernel-trace -d DIR -o tta --output-format csv -- python tools/tta_time.py scored --trace-only
 """
 import argparse
@@ -53,6 +58,7 @@ SHAPES = ((1, 10, 10, 512), (4, 10, 10, 512))
 DISTANCE = 5.0
 NUMS = (2, 3)
 ENTROPY_SHAPES = ((1, 10, 500, 128), (4, 10, 500, 128), (1, 10, 10, 512))
+PARTS_SHAPES = ((1, 10, 10, 512), (4, 10, 10, 512), (1, 10, 500, 128), (4, 10, 500, 128))
 # kernel and template argument -> the name its medians go by in each subcommand's result
 SCORED_KERNELS = {"tta_window_kernel": "window", "tta_merge_kernel<kScored>": "merge_scored",
                   "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<true>": "tile_scored",
@@ -61,6 +67,8 @@ PEAKS_KERNELS = {"tta_masked_tile_kernel": "tta_masked_tile_kernel", "tta_merge_
                  "tta_merge_kernel<kPlain>": "tta_merge_kernel", "tta_tile_kernel<false>": "tta_tile_kernel"}
 ENTROPY_KERNELS = {"tta_tile_entropy_kernel": "tile_entropy", "tta_merge_kernel<kEntropy>": "merge_entropy",
                    "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<false>": "tile_plain"}
+PARTS_KERNELS = {"tta_tile_parts_kernel": "tile_parts", "tta_parts_merge_kernel": "merge_parts",
+                 "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<false>": "tile_plain"}
 
 
 def median_us(f, warmup, iters):
@@ -109,14 +117,15 @@ def kernel_medians(path, names):
         for row in csv.DictReader(fh):
             name = row["Kernel_Name"]
             kernel = next((k for k in ("tta_window_kernel", "tta_masked_tile_kernel", "tta_merge_kernel",
-                                       "tta_tile_kernel", "tta_tile_entropy_kernel") if k in name), None)
+                                       "tta_tile_kernel", "tta_tile_entropy_kernel", "tta_tile_parts_kernel",
+                                       "tta_parts_merge_kernel") if k in name), None)
             if kernel == "tta_tile_kernel":     # the template argument, demangled or mangled
                 kernel += "<true>" if ("<true>" in name or "ILb1" in name) else "<false>"
             elif kernel == "tta_merge_kernel":
                 kernel += "<" + ("kPlain", "kScored", "kPeaks", "kEntropy")[int(re.search(r"Variant\)?E?([0123])", name).group(1))] + ">"
             if kernel not in names:
                 continue
-            grid = "x".join(str(row.get(f"Grid_Size_{d}", "?")) for d in ("XYZ" if "entropy" in kernel else "XY"))
+            grid = "x".join(str(row.get(f"Grid_Size_{d}", "?")) for d in ("XYZ" if "entropy" in kernel or "parts" in kernel else "XY"))
             by.setdefault(f"{names[kernel]}_grid{grid}", []).append(
                 (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
     return {k: dict(median_us=round(statistics.median(v), 2), launches=len(v)) for k, v in sorted(by.items())}
@@ -347,10 +356,71 @@ def run_entropy(a):
                   summary=summary, rows=rows), ENTROPY_KERNELS)
 
 
+# ------------------------------------------------------------------------------------------ parts
+def parts_composition(maps, theta, chunk=10):
+    """The outputs of tta_reduce_parts from the ops that exist without it: the average written, its
+    maximum and argmax over the tokens, and the tokens' sum chunk by chunk (each chunk's tokens in one
+    reduction, then the chunks in one: the fewest launches that keep the chunked order of the adds)."""
+    B, C, n, S, _ = maps.shape
+    pos, avg = ops.tta_reduce(maps, theta, return_avg=True)
+    value, label = avg.max(dim=1)
+    if n % chunk == 0:
+        mass = avg.view(B, n // chunk, chunk, S, S).sum(dim=2).sum(dim=1)
+    else:
+        mass = torch.stack([avg[:, t:t + chunk].sum(dim=1) for t in range(0, n, chunk)], dim=1).sum(dim=1)
+    return pos, label, value, mass
+
+
+def run_parts(a):
+    rows, summary = [], []
+    for (B, C, n, S), maps, theta, ws, pos in cases(PARTS_SHAPES):
+        wsp = torch.empty(lib().skp_tta_reduce_parts_workspace(B, n, S) // 8, device=DEV, dtype=torch.int64)
+        label = torch.empty(B, S, S, device=DEV, dtype=torch.int16)
+        value, mass = torch.empty(B, S, S, device=DEV), torch.empty(B, S, S, device=DEV)
+
+        def plain():
+            call("skp_tta_reduce", ptr(maps), B, C, n, S, ptr(theta), ptr(pos), None, ptr(ws), stream(DEV))
+
+        def parts():
+            call("skp_tta_reduce_parts", ptr(maps), B, C, n, S, ptr(theta), ptr(pos), ptr(label), ptr(value), ptr(mass),
+                 None, ptr(wsp), stream(DEV))
+
+        if a.trace_only:
+            trace(plain, parts)
+            continue
+        # (c) moves the fused reduce with the average written, then reads the average twice (max, sum)
+        comp_bytes = ops.tta_reduce_bytes(B, C, n, S, True) + 4 * B * n * S * S * 2
+        a_, spread, b_, c_ = a_b_a_c(a, rows, f"B{B}_C{C}_n{n}_S{S}", "skp_tta_reduce_parts", plain, parts,
+                                     lambda: parts_composition(maps, theta), ops.tta_reduce_bytes(B, C, n, S),
+                                     ops.tta_reduce_parts_bytes(B, C, n, S), comp_bytes)
+        got = ops.tta_reduce_parts(maps, theta)
+        want = parts_composition(maps, theta)
+        summary.append(dict(shape=[B, C, n, S], a_us=round(a_, 2), a_spread_us=round(spread, 2), b_us=round(b_, 2),
+                            c_us=round(c_, 2), b_minus_a_us=round(b_ - a_, 2), b_over_a=round(b_ / a_, 3),
+                            b_over_c=round(b_ / c_, 3), b_below_c_by_more_than_spread=bool(b_ < c_ - spread),
+                            b_below_a=bool(b_ < a_),
+                            pos_agree=bool(torch.equal(got[0], want[0])),
+                            label_agree=bool(torch.equal(got[1].long(), want[1])),
+                            value_agree=bool(torch.equal(got[2], want[2])),
+                            mass_max_rel_vs_torch_order=float(((got[3] - want[3]).abs() / want[3].abs().clamp_min(1e-30)).max())))
+        print(json.dumps(summary[-1]), flush=True)
+    if a.trace_only:
+        return
+    write(a, dict(device=torch.cuda.get_device_name(0), warmup=a.warmup, iters=a.iters,
+                  note="median of iters, launches between two HIP events; a = skp_tta_reduce (the lower of two medians, "
+                       "their difference = a_spread), b = skp_tta_reduce_parts, c = the composition ops.tta_reduce("
+                       "return_avg=True) + avg.max(dim=1) + the sum over the tokens chunk by chunk in torch (host time "
+                       "between its launches included); no average written by a or b; label_agree compares with "
+                       "torch.max's index, which is the first maximum on these continuous random maps; kernels = "
+                       "per-kernel medians of a kernel trace taken in a run of its own",
+                  summary=summary, rows=rows), PARTS_KERNELS)
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="which", required=True)
-    for name, run in (("reduce", run_reduce), ("scored", run_scored), ("peaks", run_peaks), ("entropy", run_entropy)):
+    for name, run in (("reduce", run_reduce), ("scored", run_scored), ("peaks", run_peaks), ("entropy", run_entropy),
+                      ("parts", run_parts)):
         p = sub.add_parser(name)
         p.set_defaults(run=run)
         p.add_argument("--out", default=None)
