@@ -67,6 +67,11 @@ def _reproducible_convolutions():
 AUG_BATCH_PIXELS = 10 * 512 * 512
 
 
+def _copy_major(per, copies):
+    """``run_and_find_attn_per_image``'s ``per[controller][copy]`` maps as one tensor, copy by copy."""
+    return torch.stack([per[k][b] for b in range(copies) for k in range(len(per))])
+
+
 @torch.no_grad()
 def run_image_with_context_augmented(ldm, image, context, indices, device="cuda",
                                      from_where=("down_cross", "mid_cross", "up_cross"), layers=(0, 1, 2, 3, 4, 5),
@@ -134,7 +139,7 @@ def run_image_with_context_augmented(ldm, image, context, indices, device="cuda"
                 per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level,
                                                             device=device, layers=layers, upsample_res=upscale_size,
                                                             indices=indices, controllers=controllers)
-                maps = torch.stack([per[k][b] for b in range(aug.shape[0]) for k in range(len(per))])
+                maps = _copy_major(per, aug.shape[0])
         num_samples += T.inverse(torch.ones_like(maps)).sum(dim=0)
         sum_samples += T.inverse(maps).sum(dim=0)
         done += c
@@ -232,6 +237,54 @@ def evaluate(ldm, context, indices, regressor, device="cuda", from_where=("down_
     return mean
 
 
+def _images_per_pass(image_batch, pixels, C, n, S):
+    """How many images' copies one capture pass holds: ``image_batch`` as given, else what
+    ``AUG_BATCH_PIXELS`` allows and what keeps the pass's maps below 2^31 elements; at least 1."""
+    if image_batch is not None:
+        return max(1, int(image_batch))
+    return max(1, min(AUG_BATCH_PIXELS // (pixels * C), (2 ** 31 - 1) // max(1, C * n * S * S)))
+
+
+def _tta_passes(name, ldm, images, context, indices, device, layers, noise_level, augment_degrees, augment_scale,
+                augment_translate, augmentation_iterations, controllers, upscale_size, image_batch):
+    """The capture passes of ``predict_keypoints``, ``correspond_images`` and ``part_maps`` (``name``
+    is the caller's, for the messages).  ``images`` (M, 3, H, W) or (3, H, W) in [0, 1]; for image 0,
+    then image 1, … C = ``augmentation_iterations`` thetas are drawn, each by one ``draw_theta(1)`` on
+    the global CPU generator.  A pass warps the C copies of ``_images_per_pass`` whole images, captures
+    the maps of ``indices`` per copy at ``upscale_size`` under ``_reproducible_convolutions`` and yields
+    ``(i0, nb, maps, th_inv)``: the pass's first image and image count, its maps (nb, C, n, S, S) and
+    the copies' inverse thetas (nb, C, 2, 3) on ``device``.  The generator keeps no reference to a
+    pass's maps; a caller that drops its own before asking for the next pass holds one pass at a time."""
+    from .optimize import _world
+    if _world()[0] > 1:
+        raise ValueError(f"{name} runs in a single process (world size must be 1)")
+    imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
+    if imgs.dim() == 3:
+        imgs = imgs[None]
+    if imgs.dim() != 4 or imgs.shape[1] != 3:
+        raise ValueError(f"images must be (M, 3, H, W) or (3, H, W), got {tuple(imgs.shape)}")
+    imgs = imgs.to(device, torch.float32)
+    M, C, S, n = imgs.shape[0], int(augmentation_iterations), int(upscale_size), len(indices)
+    if C < 1:
+        raise ValueError("augmentation_iterations must be at least 1")
+    T = RandomAffineWithInverse(degrees=augment_degrees, scale=augment_scale, translate=augment_translate)
+    theta = torch.cat([T.draw_theta(1) for _ in range(M * C)]).reshape(M, C, 2, 3)
+    per_pass = _images_per_pass(image_batch, imgs.shape[-1] * imgs.shape[-2], C, n, S)
+    for i0 in range(0, M, per_pass):
+        nb = min(per_pass, M - i0)
+        aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
+        with _reproducible_convolutions():
+            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
+                                                        layers=layers, upsample_res=S, indices=indices,
+                                                        controllers=controllers)
+        maps = _copy_major(per, nb * C)
+        del per, aug
+        if tuple(maps.shape) != (nb * C, n, S, S):
+            raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
+        yield i0, nb, maps.reshape(nb, C, n, S, S), T.theta_inverse().reshape(nb, C, 2, 3).to(device)
+        del maps
+
+
 KeypointScores = collections.namedtuple("KeypointScores", ["peak", "concentration", "coverage", "refined"])
 KeypointPeaks = collections.namedtuple("KeypointPeaks", ["pos", "value"])
 
@@ -276,10 +329,11 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
     alone; ``return_maps`` gives the unmasked averages.  ``return_scores`` together with
     ``num_subjects`` > 1 raises: each needs its own reduce.  Single process only: under a process
     group of more than one rank it raises.
+
+    Like ``correspond_images`` and ``part_maps``, the default images per pass also keep a pass's
+    captured maps below 2^31 elements.  That splits only a default pass that the reduce refused
+    ("maps of 2^31 elements or more"): every call that succeeded before runs the same passes.
     """
-    from .optimize import _world
-    if _world()[0] > 1:
-        raise ValueError("predict_keypoints runs in a single process (world size must be 1)")
     if max_loc_strategy not in ("argmax", "weighted_avg"):
         raise ValueError("max_loc_strategy must be 'argmax' or 'weighted_avg'")
     k = int(num_subjects)
@@ -287,48 +341,25 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
         raise ValueError("num_subjects must be at least 1")
     if k > 1 and return_scores:
         raise ValueError("return_scores and num_subjects > 1 each need their own reduce: ask for one of them")
-    imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
-    if imgs.dim() == 3:
-        imgs = imgs[None]
-    if imgs.dim() != 4 or imgs.shape[1] != 3:
-        raise ValueError(f"images must be (B, 3, H, W) or (3, H, W), got {tuple(imgs.shape)}")
-    imgs = imgs.to(device, torch.float32)
-    B, C, S = imgs.shape[0], int(augmentation_iterations), int(upscale_size)
-    if C < 1:
-        raise ValueError("augmentation_iterations must be at least 1")
-    n = len(indices)
-    T = RandomAffineWithInverse(degrees=augment_degrees, scale=augment_scale, translate=augment_translate)
-    theta = torch.cat([T.draw_theta(1) for _ in range(B * C)]).reshape(B, C, 2, 3)
-    if image_batch is None:
-        image_batch = AUG_BATCH_PIXELS // (imgs.shape[-1] * imgs.shape[-2] * C)
-    per_pass = max(1, int(image_batch))
+    S, n = int(upscale_size), len(indices)
     weighted = max_loc_strategy == "weighted_avg"
     want_avg = weighted or return_maps
     pos, avgs, refs, scos, pks, vals = [], [], [], [], [], []
-    for i0 in range(0, B, per_pass):
-        nb = min(per_pass, B - i0)
-        aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
-        with _reproducible_convolutions():
-            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
-                                                        layers=layers, upsample_res=S, indices=indices,
-                                                        controllers=controllers)
-        maps = torch.stack([per[k][b] for b in range(nb * C) for k in range(len(per))])
-        if tuple(maps.shape) != (nb * C, n, S, S):
-            raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
-        th_inv = T.theta_inverse().reshape(nb, C, 2, 3).to(device)
+    for _, nb, maps, th_inv in _tta_passes("predict_keypoints", ldm, images, context, indices, device, layers,
+                                           noise_level, augment_degrees, augment_scale, augment_translate,
+                                           augmentation_iterations, controllers, S, image_batch):
         if return_scores:
-            p, ref, sco, avg = ops.tta_reduce_scored(maps.reshape(nb, C, n, S, S), th_inv, distance=score_distance,
-                                                     return_avg=want_avg)
+            p, ref, sco, avg = ops.tta_reduce_scored(maps, th_inv, distance=score_distance, return_avg=want_avg)
             refs.append(ref)
             scos.append(sco)
         elif k > 1:
-            pk, val, avg = ops.tta_reduce_peaks(maps.reshape(nb, C, n, S, S), th_inv, k, return_avg=want_avg)
+            pk, val, avg = ops.tta_reduce_peaks(maps, th_inv, k, return_avg=want_avg)
             p = pk[:, :, 0].contiguous()
             pks.append(pk)
             vals.append(val)
         else:
-            p, avg = ops.tta_reduce(maps.reshape(nb, C, n, S, S), th_inv, return_avg=want_avg)
-        del maps, per
+            p, avg = ops.tta_reduce(maps, th_inv, return_avg=want_avg)
+        del maps
         if weighted:   # pixel_from_weighted_avg zeroes its input in place: the returned maps stay whole
             p = pixel_from_weighted_avg(avg.clone().reshape(nb * n, S, S) if return_maps else
                                         avg.reshape(nb * n, S, S)).reshape(nb, n, 2)
@@ -336,6 +367,7 @@ def predict_keypoints(ldm, images, context, indices, regressor=None, device="cud
         if return_maps:
             avgs.append(avg)
     kp = torch.cat(pos) / S
+    B = kp.shape[0]
     out = [kp]
     if regressor is not None:
         W = regressor.to(kp.device, torch.float32)
@@ -420,20 +452,7 @@ def correspond_images(ldm, images, context, num_points=10, candidates=None, devi
     float64 the sums and ``image_entropy`` (M, n_cand) float64, both in candidate order.  Single
     process only: under a process group of more than one rank it raises.
     """
-    from .optimize import _world
-    if _world()[0] > 1:
-        raise ValueError("correspond_images runs in a single process (world size must be 1)")
-    imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
-    if imgs.dim() == 3:
-        imgs = imgs[None]
-    if imgs.dim() != 4 or imgs.shape[1] != 3:
-        raise ValueError(f"images must be (M, 3, H, W) or (3, H, W), got {tuple(imgs.shape)}")
-    imgs = imgs.to(device, torch.float32)
-    M, C, S = imgs.shape[0], int(augmentation_iterations), int(upscale_size)
-    if M < 1:
-        raise ValueError("at least one image is needed")
-    if C < 1:
-        raise ValueError("augmentation_iterations must be at least 1")
+    C, S = int(augmentation_iterations), int(upscale_size)
     if S < 2:
         raise ValueError("upscale_size must be at least 2")
     if candidates is None:
@@ -446,27 +465,16 @@ def correspond_images(ldm, images, context, num_points=10, candidates=None, devi
         raise ValueError(f"one image's captured maps ({C} x {n} x {S} x {S}) reach 2^31 elements: rank fewer "
                          "candidates at a time or lower upscale_size")
     k = max(0, min(int(num_points), n))
-    T = RandomAffineWithInverse(degrees=augment_degrees, scale=augment_scale, translate=augment_translate)
-    theta = torch.cat([T.draw_theta(1) for _ in range(M * C)]).reshape(M, C, 2, 3)
-    if image_batch is None:
-        image_batch = min(AUG_BATCH_PIXELS // (imgs.shape[-1] * imgs.shape[-2] * C), (2 ** 31 - 1) // (C * n * S * S))
-    per_pass = max(1, int(image_batch))
     pos, ents = [], []
-    for i0 in range(0, M, per_pass):
-        nb = min(per_pass, M - i0)
-        aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
-        with _reproducible_convolutions():
-            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
-                                                        layers=layers, upsample_res=S, indices=candidates,
-                                                        controllers=controllers)
-        maps = torch.stack([per[c][b] for b in range(nb * C) for c in range(len(per))])
-        if tuple(maps.shape) != (nb * C, n, S, S):
-            raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
-        th_inv = T.theta_inverse().reshape(nb, C, 2, 3).to(device)
-        p, e, _ = ops.tta_reduce_entropy(maps.reshape(nb, C, n, S, S), th_inv, scale=entropy_scale)
-        del maps, per
+    for _, _, maps, th_inv in _tta_passes("correspond_images", ldm, images, context, candidates, device, layers,
+                                          noise_level, augment_degrees, augment_scale, augment_translate, C,
+                                          controllers, S, image_batch):
+        p, e, _ = ops.tta_reduce_entropy(maps, th_inv, scale=entropy_scale)
+        del maps
         pos.append(p)
         ents.append(e)
+    if not pos:
+        raise ValueError("at least one image is needed")
     image_entropy = torch.cat(ents)
     entropy = _sum_in_order(image_entropy)
     order = _rank_ascending(entropy, k)
@@ -501,20 +509,7 @@ def part_maps(ldm, images, context, indices=None, device="cuda", layers=(0, 1, 2
     ``upscale_size``, ``predict_keypoints``' keypoints; ``area`` (M, n) int64 the pixels each token
     owns.  Single process only: under a process group of more than one rank it raises.
     """
-    from .optimize import _world
-    if _world()[0] > 1:
-        raise ValueError("part_maps runs in a single process (world size must be 1)")
-    imgs = images if torch.is_tensor(images) else torch.as_tensor(images)
-    if imgs.dim() == 3:
-        imgs = imgs[None]
-    if imgs.dim() != 4 or imgs.shape[1] != 3:
-        raise ValueError(f"images must be (M, 3, H, W) or (3, H, W), got {tuple(imgs.shape)}")
-    imgs = imgs.to(device, torch.float32)
-    M, C, S = imgs.shape[0], int(augmentation_iterations), int(upscale_size)
-    if M < 1:
-        raise ValueError("at least one image is needed")
-    if C < 1:
-        raise ValueError("augmentation_iterations must be at least 1")
+    C, S = int(augmentation_iterations), int(upscale_size)
     if S < 2:
         raise ValueError("upscale_size must be at least 2")
     if indices is None:
@@ -528,30 +523,20 @@ def part_maps(ldm, images, context, indices=None, device="cuda", layers=(0, 1, 2
     if C * n * S * S >= 2 ** 31:
         raise ValueError(f"one image's captured maps ({C} x {n} x {S} x {S}) reach 2^31 elements: label fewer "
                          "tokens at a time or lower upscale_size")
-    T = RandomAffineWithInverse(degrees=augment_degrees, scale=augment_scale, translate=augment_translate)
-    theta = torch.cat([T.draw_theta(1) for _ in range(M * C)]).reshape(M, C, 2, 3)
-    if image_batch is None:
-        image_batch = min(AUG_BATCH_PIXELS // (imgs.shape[-1] * imgs.shape[-2] * C), (2 ** 31 - 1) // (C * n * S * S))
-    per_pass = max(1, int(image_batch))
     pos, labels, values, masses = [], [], [], []
-    for i0 in range(0, M, per_pass):
-        nb = min(per_pass, M - i0)
-        aug = T(imgs[i0:i0 + nb].repeat_interleave(C, dim=0), theta=theta[i0:i0 + nb].reshape(nb * C, 2, 3))
-        with _reproducible_convolutions():
-            per = ptp_utils.run_and_find_attn_per_image(ldm, aug, context, noise_level=noise_level, device=device,
-                                                        layers=layers, upsample_res=S, indices=indices,
-                                                        controllers=controllers)
-        maps = torch.stack([per[c][b] for b in range(nb * C) for c in range(len(per))])
-        if tuple(maps.shape) != (nb * C, n, S, S):
-            raise ValueError(f"captured maps {tuple(maps.shape)}, expected {(nb * C, n, S, S)} (one controller)")
-        th_inv = T.theta_inverse().reshape(nb, C, 2, 3).to(device)
-        p, lab, val, mas, _ = ops.tta_reduce_parts(maps.reshape(nb, C, n, S, S), th_inv)
-        del maps, per
+    for _, _, maps, th_inv in _tta_passes("part_maps", ldm, images, context, indices, device, layers, noise_level,
+                                          augment_degrees, augment_scale, augment_translate, C, controllers, S,
+                                          image_batch):
+        p, lab, val, mas, _ = ops.tta_reduce_parts(maps, th_inv)
+        del maps
         pos.append(p)
         labels.append(lab)
         values.append(val)
         masses.append(mas)
+    if not pos:
+        raise ValueError("at least one image is needed")
     mass = torch.cat(masses)
+    M = mass.shape[0]
     label = torch.cat(labels).masked_fill(mass <= float(part_threshold), -1)
     # the pixels of each label, the background in column 0 (integer adds: any order gives the same counts)
     owner = (label.long() + 1).reshape(M, S * S)

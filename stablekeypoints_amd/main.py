@@ -24,6 +24,8 @@ fewer); launching it under ``torch.distributed.run`` yourself works too (every r
 ``--seed``).
 """
 import argparse
+import contextlib
+import csv
 import os
 import sys
 
@@ -134,6 +136,38 @@ def _image_names(dataset):
     return None if names is None else list(names)
 
 
+@contextlib.contextmanager
+def _rng_restored(device):
+    """The CPU and ``device`` RNG states are on exit what they were on entry, also when the body raises."""
+    cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state(device)
+    try:
+        yield
+    finally:
+        torch.set_rng_state(cpu_state)
+        torch.cuda.set_rng_state(dev_state, device)
+
+
+def _write_rows(path, names, values):
+    """A CSV without header, one row per entry of ``values`` (M, …): the index, the entry's name where
+    ``names`` has them, then the entry's values flattened, each as ``repr(float(v))``."""
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        for i in range(values.shape[0]):
+            row = [i] + ([names[i]] if names is not None else [])
+            w.writerow(row + [repr(float(v)) for v in values[i].reshape(-1)])
+
+
+def _save_row_sheet(path, images, points, device):
+    """``path``: the first 12 of ``images`` at most in one row with their ``points``, point j in colour j,
+    downscaled by 2 when both sides are even."""
+    from . import ops
+    from .visualize import save_png
+    m = min(12, images.shape[0])
+    f = 2 if images.shape[-1] % 2 == 0 and images.shape[-2] % 2 == 0 else 1
+    sheet = ops.render_sheet(images[:m].to(device, torch.float32), None, points[:m], rows=1, cols=m, downscale=f)
+    save_png(sheet, path)
+
+
 def correspond_stage(args, ldm, controllers, embedding, dataset):
     """``--correspond``: ``eval.correspond_images`` over every image of ``dataset`` for ``--top_k`` of the
     embedding's tokens.  Writes ``correspondence_indices.pt`` (k,) int64, ``correspondence_entropy.pt``
@@ -142,29 +176,21 @@ def correspond_stage(args, ldm, controllers, embedding, dataset):
     keypoint j in colour j in every image.  The CPU and device RNG states are what they were on entry
     when it returns, so the prediction that follows draws what a plain predict run draws.  Returns
     the indices."""
-    from . import ops
     from .eval import correspond_images
-    from .visualize import save_png
     folder = args.save_folder
-    cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state(args.device)
-    images = torch.stack([torch.as_tensor(dataset[i]["img"]) for i in range(len(dataset))])
-    corr = correspond_images(ldm, images, embedding, num_points=args.top_k, device=args.device, layers=args.layers,
-                             noise_level=args.noise_level, augment_degrees=args.augment_degrees,
-                             augment_scale=args.augment_scale, augment_translate=args.augment_translate,
-                             augmentation_iterations=args.augmentation_iterations, controllers=controllers,
-                             upscale_size=args.correspond_size, entropy_scale=args.entropy_scale)
-    torch.save(corr.indices.cpu(), os.path.join(folder, "correspondence_indices.pt"))
-    torch.save(corr.entropy.cpu(), os.path.join(folder, "correspondence_entropy.pt"))
-    torch.save(corr.points.cpu(), os.path.join(folder, "correspondence_points.pt"))
-    if args.visualize:
-        m = min(12, images.shape[0])
-        f = 2 if images.shape[-1] % 2 == 0 and images.shape[-2] % 2 == 0 else 1
-        sheet = ops.render_sheet(images[:m].to(args.device, torch.float32), None, corr.points[:m], rows=1, cols=m,
-                                 downscale=f)
-        save_png(sheet, os.path.join(folder, "correspondences.png"))
-    print("correspond: indices", corr.indices.tolist(), flush=True)
-    torch.set_rng_state(cpu_state)
-    torch.cuda.set_rng_state(dev_state, args.device)
+    with _rng_restored(args.device):
+        images = torch.stack([torch.as_tensor(dataset[i]["img"]) for i in range(len(dataset))])
+        corr = correspond_images(ldm, images, embedding, num_points=args.top_k, device=args.device, layers=args.layers,
+                                 noise_level=args.noise_level, augment_degrees=args.augment_degrees,
+                                 augment_scale=args.augment_scale, augment_translate=args.augment_translate,
+                                 augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                                 upscale_size=args.correspond_size, entropy_scale=args.entropy_scale)
+        torch.save(corr.indices.cpu(), os.path.join(folder, "correspondence_indices.pt"))
+        torch.save(corr.entropy.cpu(), os.path.join(folder, "correspondence_entropy.pt"))
+        torch.save(corr.points.cpu(), os.path.join(folder, "correspondence_points.pt"))
+        if args.visualize:
+            _save_row_sheet(os.path.join(folder, "correspondences.png"), images, corr.points, args.device)
+        print("correspond: indices", corr.indices.tolist(), flush=True)
     return corr.indices
 
 
@@ -181,41 +207,36 @@ def parts_stage(args, ldm, controllers, embedding, indices, dataset):
     were on entry when it returns, so the prediction that follows draws what a plain predict run draws."""
     from . import ops
     from .eval import foreground_iou, part_maps
-    from .visualize import save_png
     folder = args.save_folder
-    cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state(args.device)
-    items = [dataset[i] for i in range(len(dataset))]
-    images = torch.stack([torch.as_tensor(it["img"]) for it in items])
-    parts = part_maps(ldm, images, embedding, None if args.part_tokens == "all" else indices.cpu(), device=args.device,
-                      layers=args.layers, noise_level=args.noise_level, augment_degrees=args.augment_degrees,
-                      augment_scale=args.augment_scale, augment_translate=args.augment_translate,
-                      augmentation_iterations=args.augmentation_iterations, controllers=controllers,
-                      upscale_size=args.part_size, part_threshold=args.part_threshold)
-    torch.save(parts.label.cpu(), os.path.join(folder, "part_labels.pt"))
-    torch.save(parts.mass.cpu(), os.path.join(folder, "part_mass.pt"))
-    torch.save(parts.area.cpu(), os.path.join(folder, "part_area.pt"))
-    torch.save(parts.points.cpu(), os.path.join(folder, "part_points.pt"))
-    if items and all("mask" in it for it in items):
-        masks = torch.stack([torch.as_tensor(it["mask"], dtype=torch.float32) for it in items])
-        iou = foreground_iou(parts.label, masks).cpu()
-        torch.save(iou, os.path.join(folder, "part_fg_iou.pt"))
-        print(f"part_maps: mean foreground IoU {float(iou.mean()):.4f} over {iou.shape[0]} images", flush=True)
-    if args.visualize:
-        m = min(12, images.shape[0])
-        H, W = images.shape[-2:]
-        n = parts.points.shape[1]
-        shown = images[:m].to(args.device, torch.float32)
-        label = torch.nn.functional.interpolate(parts.label[:m, None].float(), size=(H, W), mode="nearest")[:, 0].long()
-        colors = ops.default_colors(n).to(args.device)
-        tint = (colors.float() / 255.0)[label.clamp_min(0)].permute(0, 3, 1, 2)
-        shown = torch.where((label >= 0)[:, None], 0.5 * shown + 0.5 * tint, shown)
-        f = 2 if W % 2 == 0 and H % 2 == 0 else 1
-        sheet = ops.render_sheet(shown, None, parts.points[:m], rows=1, cols=m, downscale=f)
-        save_png(sheet, os.path.join(folder, "parts.png"))
-    print(f"part_maps: {images.shape[0]} images, {parts.points.shape[1]} tokens at {args.part_size} -> "
-          f"{os.path.join(folder, 'part_labels.pt')}", flush=True)
-    torch.set_rng_state(cpu_state)
-    torch.cuda.set_rng_state(dev_state, args.device)
+    with _rng_restored(args.device):
+        items = [dataset[i] for i in range(len(dataset))]
+        images = torch.stack([torch.as_tensor(it["img"]) for it in items])
+        parts = part_maps(ldm, images, embedding, None if args.part_tokens == "all" else indices.cpu(),
+                          device=args.device, layers=args.layers, noise_level=args.noise_level,
+                          augment_degrees=args.augment_degrees, augment_scale=args.augment_scale,
+                          augment_translate=args.augment_translate,
+                          augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                          upscale_size=args.part_size, part_threshold=args.part_threshold)
+        torch.save(parts.label.cpu(), os.path.join(folder, "part_labels.pt"))
+        torch.save(parts.mass.cpu(), os.path.join(folder, "part_mass.pt"))
+        torch.save(parts.area.cpu(), os.path.join(folder, "part_area.pt"))
+        torch.save(parts.points.cpu(), os.path.join(folder, "part_points.pt"))
+        if items and all("mask" in it for it in items):
+            masks = torch.stack([torch.as_tensor(it["mask"], dtype=torch.float32) for it in items])
+            iou = foreground_iou(parts.label, masks).cpu()
+            torch.save(iou, os.path.join(folder, "part_fg_iou.pt"))
+            print(f"part_maps: mean foreground IoU {float(iou.mean()):.4f} over {iou.shape[0]} images", flush=True)
+        if args.visualize:
+            m = min(12, images.shape[0])
+            shown = images[:m].to(args.device, torch.float32)
+            label = torch.nn.functional.interpolate(parts.label[:m, None].float(), size=tuple(images.shape[-2:]),
+                                                    mode="nearest")[:, 0].long()
+            colors = ops.default_colors(parts.points.shape[1]).to(args.device)
+            tint = (colors.float() / 255.0)[label.clamp_min(0)].permute(0, 3, 1, 2)
+            shown = torch.where((label >= 0)[:, None], 0.5 * shown + 0.5 * tint, shown)
+            _save_row_sheet(os.path.join(folder, "parts.png"), shown, parts.points, args.device)
+        print(f"part_maps: {images.shape[0]} images, {parts.points.shape[1]} tokens at {args.part_size} -> "
+              f"{os.path.join(folder, 'part_labels.pt')}", flush=True)
 
 
 def predict_stage(args, ldm, controllers, batch=4):
@@ -236,7 +257,6 @@ def predict_stage(args, ldm, controllers, batch=4):
     ``indices.pt``, and ``regressor.pt`` is not applied (it was fitted to other tokens).
     With ``--part_maps`` ``parts_stage`` first writes the part maps of the same images; the keypoints are
     the same bits with and without it."""
-    import csv
     from .datasets import make_dataset
     from .eval import predict_keypoints
     folder = args.save_folder
@@ -266,56 +286,38 @@ def predict_stage(args, ldm, controllers, batch=4):
                                 augmentation_iterations=args.augmentation_iterations,
                                 max_loc_strategy=args.max_loc_strategy, controllers=controllers,
                                 return_scores=args.keypoint_scores, num_subjects=k)
+        out = list(out) if isinstance(out, tuple) else [out]
+        # predict_keypoints refuses num_subjects > 1 with return_scores: at most one trailing output
+        last = out.pop() if k > 1 or args.keypoint_scores else None
         if k > 1:
-            pk = out[-1]
-            out = out[0] if len(out) == 2 else out[:-1]
-            pks.append(pk.pos.cpu())
-            vals.append(pk.value.cpu())
+            pks.append(last.pos.cpu())
+            vals.append(last.value.cpu())
         if args.keypoint_scores:
-            sc = out[-1]
-            out = out[0] if len(out) == 2 else out[:-1]
-            scos.append(torch.stack([sc.peak, sc.concentration, sc.coverage], dim=-1).cpu())
-            refs.append(sc.refined.cpu())
-        kp, reg = out if regressor is not None else (out, None)
-        kps.append(kp.cpu())
-        if reg is not None:
-            regs.append(reg.cpu())
+            scos.append(torch.stack([last.peak, last.concentration, last.coverage], dim=-1).cpu())
+            refs.append(last.refined.cpu())
+        kps.append(out[0].cpu())
+        if regressor is not None:
+            regs.append(out[1].cpu())
     n = len(indices)
     kps = torch.cat(kps) if kps else torch.zeros(0, n, 2)
     torch.save(kps, os.path.join(folder, "keypoints.pt"))
     if regressor is not None:
         regs = torch.cat(regs) if regs else torch.zeros(0, regressor.shape[1] // 2, 2)
         torch.save(regs, os.path.join(folder, "regressed_keypoints.pt"))
-    with open(os.path.join(folder, "keypoints.csv"), "w", newline="") as fh:
-        w = csv.writer(fh)
-        for i in range(kps.shape[0]):
-            row = [i] + ([names[i]] if names is not None else [])
-            row += [repr(float(v)) for v in kps[i].reshape(-1)]
-            if regressor is not None:
-                row += [repr(float(v)) for v in regs[i].reshape(-1)]
-            w.writerow(row)
+    _write_rows(os.path.join(folder, "keypoints.csv"), names,
+                kps.flatten(1) if regressor is None else torch.cat([kps.flatten(1), regs.flatten(1)], dim=1))
     if args.keypoint_scores:
         scos = torch.cat(scos) if scos else torch.zeros(0, n, 3)
         refs = torch.cat(refs) if refs else torch.zeros(0, n, 2)
         torch.save(scos, os.path.join(folder, "keypoint_scores.pt"))
         torch.save(refs, os.path.join(folder, "refined_keypoints.pt"))
-        with open(os.path.join(folder, "keypoint_scores.csv"), "w", newline="") as fh:
-            w = csv.writer(fh)
-            for i in range(scos.shape[0]):
-                row = [i] + ([names[i]] if names is not None else [])
-                row += [repr(float(v)) for v in torch.cat([refs[i], scos[i]], dim=-1).reshape(-1)]
-                w.writerow(row)
+        _write_rows(os.path.join(folder, "keypoint_scores.csv"), names, torch.cat([refs, scos], dim=-1))
     if k > 1:
         pks = torch.cat(pks) if pks else torch.zeros(0, n, k, 2)
         vals = torch.cat(vals) if vals else torch.zeros(0, n, k)
         torch.save(pks, os.path.join(folder, "subject_keypoints.pt"))
         torch.save(vals, os.path.join(folder, "subject_peak_values.pt"))
-        with open(os.path.join(folder, "subject_keypoints.csv"), "w", newline="") as fh:
-            w = csv.writer(fh)
-            for i in range(pks.shape[0]):
-                row = [i] + ([names[i]] if names is not None else [])
-                row += [repr(float(v)) for v in torch.cat([pks[i], vals[i][..., None]], dim=-1).reshape(-1)]
-                w.writerow(row)
+        _write_rows(os.path.join(folder, "subject_keypoints.csv"), names, torch.cat([pks, vals[..., None]], dim=-1))
     print(f"predict: {kps.shape[0]} images, {n} keypoints each -> {os.path.join(folder, 'keypoints.pt')}", flush=True)
 
 

@@ -2157,6 +2157,23 @@ def _tta_workspace(op, dev, B, n, S, num=None, radius2=None):
     return ws
 
 
+def _tta_call(op, maps, theta_inv, return_avg, query):
+    """What the TTA reduces share around their one ``skp_<op>`` call.  After ``_tta_inputs``,
+    ``query(B, C, n, S)`` checks the query's own arguments and returns ``(scalars, pos_shape, extras,
+    nbytes, ws_args)``: the scalars that ``skp_<op>`` takes after ``theta_inv``, the shape of ``pos``,
+    a ``(shape, dtype)`` per further output in the entry point's order, the byte model's value and the
+    workspace query's further arguments.  Returns ``(pos, *extras, avg)``: ``avg`` (B, n, S, S) when
+    ``return_avg``, else None."""
+    maps, th, B, C, n, S, dev = _tta_inputs(op, maps, theta_inv)
+    scalars, pos_shape, extras, nbytes, ws_args = query(B, C, n, S)
+    ws = _tta_workspace(op, dev, B, n, S, *ws_args)
+    outs = [torch.empty(*shape, device=dev, dtype=dtype) for shape, dtype in [(pos_shape, F32), *extras]]
+    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
+    with _timed(f"skp_{op}", nbytes):
+        call(f"skp_{op}", ptr(maps), B, C, n, S, ptr(th), *scalars, *map(ptr, outs), ptr(avg), ptr(ws), stream(dev))
+    return (*outs, avg)
+
+
 def tta_reduce_bytes(B, C, n, S, avg=False):
     """Byte model of skp_tta_reduce: every captured map read once, the average written on request."""
     return 4 * B * C * n * S * S + (4 * B * n * S * S if avg else 0)
@@ -2171,13 +2188,10 @@ def tta_reduce(maps, theta_inv, return_avg=False):
     average (B, n, S, S) when ``return_avg``, else None.  Bit-identical to ``affine_warp`` per
     copy, sums in copy order, the division, the NaN fix and ``find_max_pixel``.
     """
-    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce", maps, theta_inv)
-    ws = _tta_workspace("tta_reduce", dev, B, n, S)
-    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
-    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
-    with _timed("skp_tta_reduce", tta_reduce_bytes(B, C, n, S, return_avg)):
-        call("skp_tta_reduce", ptr(maps), B, C, n, S, ptr(th), ptr(pos), ptr(avg), ptr(ws), stream(dev))
-    return pos, avg
+    def query(B, C, n, S):
+        return (), (B, n, 2), [], tta_reduce_bytes(B, C, n, S, return_avg), ()
+
+    return _tta_call("tta_reduce", maps, theta_inv, return_avg, query)
 
 
 def tta_reduce_scored_bytes(B, C, n, S, distance=5, avg=False):
@@ -2197,19 +2211,14 @@ def tta_reduce_scored(maps, theta_inv, distance=5, return_avg=False):
     the peak over its whole mass) and the coverage (``[..., 2]``: the share of the C copies that
     saw the peak pixel).  The average is not written unless ``return_avg``.  ``0 < distance <= 16``.
     """
-    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_scored", maps, theta_inv)
-    distance = float(distance)
-    if not 0.0 < distance <= 16.0:
-        raise ValueError(f"tta_reduce_scored: distance must be in (0, 16], got {distance}")
-    ws = _tta_workspace("tta_reduce_scored", dev, B, n, S)
-    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
-    refined = torch.empty(B, n, 2, device=dev, dtype=F32)
-    scores = torch.empty(B, n, 3, device=dev, dtype=F32)
-    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
-    with _timed("skp_tta_reduce_scored", tta_reduce_scored_bytes(B, C, n, S, distance, return_avg)):
-        call("skp_tta_reduce_scored", ptr(maps), B, C, n, S, ptr(th), distance, ptr(pos), ptr(refined), ptr(scores),
-             ptr(avg), ptr(ws), stream(dev))
-    return pos, refined, scores, avg
+    def query(B, C, n, S):
+        d = float(distance)
+        if not 0.0 < d <= 16.0:
+            raise ValueError(f"tta_reduce_scored: distance must be in (0, 16], got {d}")
+        refined_scores = [((B, n, 2), F32), ((B, n, 3), F32)]
+        return (d,), (B, n, 2), refined_scores, tta_reduce_scored_bytes(B, C, n, S, d, return_avg), ()
+
+    return _tta_call("tta_reduce_scored", maps, theta_inv, return_avg, query)
 
 
 def tta_reduce_peaks_bytes(B, C, n, S, num, radius=None, avg=False):
@@ -2234,21 +2243,17 @@ def tta_reduce_peaks(maps, theta_inv, num, radius=None, return_avg=False):
     ``radius=None`` is the reference's 0.05 · S.  ``1 <= num <= 16``.  The average is not in memory
     unless ``return_avg``.
     """
-    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_peaks", maps, theta_inv)
-    num = int(num)
-    if not 1 <= num <= 16:
-        raise ValueError(f"tta_reduce_peaks: num must be in [1, 16], got {num}")
-    radius2 = _radius2(S) if radius is None else float(radius) ** 2
-    if not 0.0 < radius2 < float("inf"):
-        raise ValueError(f"tta_reduce_peaks: radius must be positive and finite, got {radius}")
-    ws = _tta_workspace("tta_reduce_peaks", dev, B, n, S, num, radius2)
-    pos = torch.empty(B, n, num, 2, device=dev, dtype=F32)
-    values = torch.empty(B, n, num, device=dev, dtype=F32)
-    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
-    with _timed("skp_tta_reduce_peaks", tta_reduce_peaks_bytes(B, C, n, S, num, radius, return_avg)):
-        call("skp_tta_reduce_peaks", ptr(maps), B, C, n, S, ptr(th), num, radius2, ptr(pos), ptr(values), ptr(avg),
-             ptr(ws), stream(dev))
-    return pos, values, avg
+    def query(B, C, n, S):
+        k = int(num)
+        if not 1 <= k <= 16:
+            raise ValueError(f"tta_reduce_peaks: num must be in [1, 16], got {k}")
+        radius2 = _radius2(S) if radius is None else float(radius) ** 2
+        if not 0.0 < radius2 < float("inf"):
+            raise ValueError(f"tta_reduce_peaks: radius must be positive and finite, got {radius}")
+        nbytes = tta_reduce_peaks_bytes(B, C, n, S, k, radius, return_avg)
+        return (k, radius2), (B, n, k, 2), [((B, n, k), F32)], nbytes, (k, radius2)
+
+    return _tta_call("tta_reduce_peaks", maps, theta_inv, return_avg, query)
 
 
 def tta_reduce_entropy_bytes(B, C, n, S, avg=False):
@@ -2268,18 +2273,13 @@ def tta_reduce_entropy(maps, theta_inv, scale=1.0, return_avg=False):
     orders).  A plane whose maximum is +inf gives NaN.  The average is not in memory unless
     ``return_avg``.  ``scale`` must be positive and finite.
     """
-    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_entropy", maps, theta_inv)
-    scale = float(scale)
-    if not 0.0 < scale < float("inf"):
-        raise ValueError(f"tta_reduce_entropy: scale must be positive and finite, got {scale}")
-    ws = _tta_workspace("tta_reduce_entropy", dev, B, n, S)
-    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
-    entropy = torch.empty(B, n, device=dev, dtype=torch.float64)
-    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
-    with _timed("skp_tta_reduce_entropy", tta_reduce_entropy_bytes(B, C, n, S, return_avg)):
-        call("skp_tta_reduce_entropy", ptr(maps), B, C, n, S, ptr(th), scale, ptr(pos), ptr(entropy), ptr(avg),
-             ptr(ws), stream(dev))
-    return pos, entropy, avg
+    def query(B, C, n, S):
+        s = float(scale)
+        if not 0.0 < s < float("inf"):
+            raise ValueError(f"tta_reduce_entropy: scale must be positive and finite, got {s}")
+        return (s,), (B, n, 2), [((B, n), torch.float64)], tta_reduce_entropy_bytes(B, C, n, S, return_avg), ()
+
+    return _tta_call("tta_reduce_entropy", maps, theta_inv, return_avg, query)
 
 
 def tta_reduce_parts_bytes(B, C, n, S, avg=False):
@@ -2302,16 +2302,10 @@ def tta_reduce_parts(maps, theta_inv, return_avg=False):
     covers has label 0, value 0 and mass 0.  The average is not in memory unless ``return_avg``.
     ``n <= 32767``.
     """
-    maps, th, B, C, n, S, dev = _tta_inputs("tta_reduce_parts", maps, theta_inv)
-    if n > 32767:
-        raise ValueError(f"tta_reduce_parts: at most 32767 tokens (the label is int16), got {n}")
-    ws = _tta_workspace("tta_reduce_parts", dev, B, n, S)
-    pos = torch.empty(B, n, 2, device=dev, dtype=F32)
-    label = torch.empty(B, S, S, device=dev, dtype=torch.int16)
-    value = torch.empty(B, S, S, device=dev, dtype=F32)
-    mass = torch.empty(B, S, S, device=dev, dtype=F32)
-    avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
-    with _timed("skp_tta_reduce_parts", tta_reduce_parts_bytes(B, C, n, S, return_avg)):
-        call("skp_tta_reduce_parts", ptr(maps), B, C, n, S, ptr(th), ptr(pos), ptr(label), ptr(value), ptr(mass),
-             ptr(avg), ptr(ws), stream(dev))
-    return pos, label, value, mass, avg
+    def query(B, C, n, S):
+        if n > 32767:
+            raise ValueError(f"tta_reduce_parts: at most 32767 tokens (the label is int16), got {n}")
+        label_value_mass = [((B, S, S), torch.int16), ((B, S, S), F32), ((B, S, S), F32)]
+        return (), (B, n, 2), label_value_mass, tta_reduce_parts_bytes(B, C, n, S, return_avg), ()
+
+    return _tta_call("tta_reduce_parts", maps, theta_inv, return_avg, query)

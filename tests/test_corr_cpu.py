@@ -2,7 +2,6 @@
 tests/corr_ref.py against the reference's recorded outputs (tests/golden/corresponding_points.npz), the
 conditions under which a ranking means something, the one-pass merged entropy formula that
 skp_tta_reduce_entropy implements, its argument checks through the C ABI, and the parser."""
-import ctypes
 import inspect
 import math
 import os
@@ -12,6 +11,7 @@ import pytest
 import torch
 
 import corr_ref
+import tta_abi
 
 GOLDEN = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "corresponding_points.npz"))
 IDS = ["x".join(map(str, s)) for s in corr_ref.CASES]
@@ -115,32 +115,10 @@ def test_ops_tta_reduce_entropy_refuses_cpu_tensors():
 
 
 def test_tta_reduce_entropy_rejects_bad_arguments_without_gpu():
-    from stablekeypoints_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("libskp.so not built")
-    L = _lib.lib()
-    a = ctypes.c_void_p(256)   # aligned non-null dummy: every check below fails before any HIP call
-    #     maps B  C  n  S  theta scale pos entropy avg  ws stream
-    ok = (a, 2, 3, 5, 37, a, 1.0, a, a, None, a, None)
-
-    def rc_with(**kw):
-        args = list(ok)
-        for k, v in kw.items():
-            args[int(k[1:])] = v
-        return L.skp_tta_reduce_entropy(*args)
-
-    for slot in (0, 5, 7, 8, 10):   # maps, theta_inv, pos, entropy, workspace
-        assert rc_with(**{f"a{slot}": None}) == -1 and b"null" in L.skp_last_error()
-    for slot in (1, 2, 3, 4):   # B, C, n, S
-        for bad in (0, -1):
-            assert rc_with(**{f"a{slot}": bad}) == -1 and b"non-positive" in L.skp_last_error()
-    assert rc_with(a4=1) == -1 and b"at least 2" in L.skp_last_error()
-    for bad in (0.0, -1.0, float("nan"), float("inf")):
-        assert rc_with(a6=bad) == -1 and b"scale" in L.skp_last_error()
-    assert rc_with(a10=ctypes.c_void_p(260)) == -1 and b"aligned" in L.skp_last_error()
-    assert rc_with(a1=1, a2=1, a3=1, a4=46341) == -1 and b"2^31" in L.skp_last_error()
-    assert rc_with(a1=8, a2=10, a3=10, a4=2048) == -1 and b"2^31" in L.skp_last_error()
-    assert rc_with(a1=65536, a2=1, a3=1, a4=2) == -1 and b"65535" in L.skp_last_error()
+    """The scale and the workspace query; the checks every reduce shares are in tests/test_tta_cpu.py."""
+    L = tta_abi.library()
+    for bad in (0.0, -1.0, float("nan"), float("inf")):     # slot 6 of skp_tta_reduce_entropy
+        assert tta_abi.rc_with(L, "skp_tta_reduce_entropy", a6=bad) == -1 and b"scale" in L.skp_last_error()
     # the workspace query: skp_tta_reduce's partials and two doubles per image, token and tile
     for B, n, S in ((1, 500, 128), (4, 500, 128), (1, 10, 512), (2, 5, 37), (1, 1, 2)):
         got = L.skp_tta_reduce_entropy_workspace(B, n, S)

@@ -18,7 +18,7 @@ import torch
 import corr_ref
 import tta_ref
 import tta_tiny
-from tta_tiny import AUG, DEV, N_TOK, R, S_UP
+from tta_tiny import DEV, N_TOK, bits as _bits, cli as _cli, correspond as _correspond, tiny  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,10 +31,6 @@ GOLDEN = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golde
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-
-
-def _bits(t):
-    return t.view(torch.int32)
 
 
 # ------------------------------------------------------------------------------------------ the kernel
@@ -152,19 +148,6 @@ def test_fused_selection_is_the_reference(planted):
 
 
 # ------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def tiny():
-    return tta_tiny.build_tiny()
-
-
-def _correspond(tiny, **kw):
-    from stablekeypoints_amd import eval as ev
-    ldm, controllers, images, ctx, _ = tiny
-    tta_tiny.seed()
-    return ev.correspond_images(ldm, images, ctx, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
-                                upscale_size=S_UP, augmentation_iterations=3, image_batch=2, **AUG, **kw)
-
-
 def test_correspond_images_tiny(tiny):
     from stablekeypoints_amd import eval as ev
     M, k = 2, 4
@@ -205,18 +188,10 @@ def test_correspond_images_candidates_tiny(tiny):
 
 def test_cli_correspond_tiny(tmp_path):
     from PIL import Image
-    from stablekeypoints_amd import main as cli, ops
+    from stablekeypoints_amd import ops
 
     def run(folder, *extra, indices=None):
-        folder.mkdir()
-        g = torch.Generator().manual_seed(7)
-        torch.save(torch.randn(1, N_TOK, 32, generator=g), folder / "embedding.pt")
-        if indices is not None:
-            torch.save(indices, folder / "indices.pt")
-        cli.main(["--model_type", "tiny", "--dataset_name", "synthetic", "--max_len", "5", "--num_tokens", str(N_TOK),
-                  "--feature_upsample_res", str(R), "--augmentation_iterations", "2", "--start_from_stage", "predict",
-                  "--top_k", "3", "--save_folder", str(folder), "--device", DEV, *extra])
-        return torch.load(folder / "keypoints.pt", weights_only=True)
+        return _cli(folder, "--top_k", "3", *extra, indices=indices)
 
     out = tmp_path / "correspond"
     kp = run(out, "--correspond", "--correspond_size", "64", "--visualize")     # no indices.pt in the folder

@@ -11,7 +11,7 @@ import torch
 
 import tta_ref
 import tta_tiny
-from tta_tiny import AUG, DEV, N_TOK, R, S_UP, predict as _predict, seed as _seed
+from tta_tiny import AUG, DEV, S_UP, cli as _cli, predict as _predict, seed as _seed, tiny  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -106,11 +106,6 @@ def test_tta_reduce_rejects_bad_shapes():
 
 
 # ------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def tiny():
-    return tta_tiny.build_tiny()
-
-
 def test_predict_keypoints_tiny(tiny):
     from stablekeypoints_amd import eval as ev
     images = tiny[2]
@@ -162,17 +157,8 @@ def test_predict_keypoints_refuses_a_process_group(tiny, monkeypatch):
 
 def test_cli_predict_stage_tiny(tmp_path):
     import csv
-    from stablekeypoints_amd import main as cli
     out = tmp_path / "run"
-    out.mkdir()
-    g = torch.Generator().manual_seed(7)
-    torch.save(torch.randn(1, N_TOK, 32, generator=g), out / "embedding.pt")
-    torch.save(torch.tensor([3, 7, 0, 12, 5]), out / "indices.pt")
-    argv = ["--model_type", "tiny", "--dataset_name", "synthetic", "--max_len", "5", "--num_tokens", str(N_TOK),
-            "--feature_upsample_res", str(R), "--augmentation_iterations", "2", "--start_from_stage", "predict",
-            "--save_folder", str(out), "--device", DEV]
-    cli.main(argv)
-    kp = torch.load(out / "keypoints.pt", weights_only=True)
+    kp = _cli(out)
     assert kp.shape == (5, 5, 2) and kp.dtype == torch.float32
     assert (kp > 0).all() and (kp < 1).all()
     rows = list(csv.reader(open(out / "keypoints.csv")))
@@ -181,8 +167,8 @@ def test_cli_predict_stage_tiny(tmp_path):
     assert not (out / "all_errors.pt").exists() and not (out / "regressed_keypoints.pt").exists()
     assert not (out / "regressor.pt").exists() and not (out / "source_keypoints.pt").exists()
     # with a saved regressor the regressed keypoints are written too
-    torch.save(torch.randn(10, 30, generator=g), out / "regressor.pt")
-    cli.main(argv)
+    torch.save(torch.randn(10, 30, generator=torch.Generator().manual_seed(8)), out / "regressor.pt")
+    _cli(out)
     reg = torch.load(out / "regressed_keypoints.pt", weights_only=True)
     assert reg.shape == (5, 15, 2) and torch.load(out / "keypoints.pt", weights_only=True).shape == kp.shape
     assert len(list(csv.reader(open(out / "keypoints.csv")))[0]) == 1 + 10 + 30

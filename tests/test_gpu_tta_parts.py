@@ -19,7 +19,8 @@ import tta_parts_ref
 import tta_ref
 import tta_tiny
 from tta_parts_ref import PARTS_SHAPES, parts_ref
-from tta_tiny import AUG, DEV, N_TOK, R, S_UP
+from tta_tiny import (DEV, N_TOK, S_UP, bits as _bits, cli as _cli, part_maps as _part_maps, same_bits as _same,
+                      tiny)  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,17 +29,6 @@ pytestmark = pytest.mark.gpu
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-
-
-def _bits(t):
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _same(got, want_np):
-    """A device tensor against a numpy array of the same dtype, bit for bit."""
-    got = got.cpu().numpy()
-    assert got.dtype == want_np.dtype and got.shape == want_np.shape
-    return np.array_equal(got.view(np.uint8), np.ascontiguousarray(want_np).view(np.uint8))
 
 
 # ------------------------------------------------------------------------------------------ the kernel
@@ -146,19 +136,6 @@ def test_tta_reduce_parts_rejects_bad_shapes():
 
 
 # ------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def tiny():
-    return tta_tiny.build_tiny()
-
-
-def _part_maps(tiny, indices, **kw):
-    from stablekeypoints_amd import eval as ev
-    ldm, controllers, images, ctx, _ = tiny
-    tta_tiny.seed()
-    return ev.part_maps(ldm, images, ctx, indices, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
-                        upscale_size=S_UP, augmentation_iterations=3, image_batch=2, **AUG, **kw)
-
-
 @pytest.mark.parametrize("every", [False, True], ids=["five_indices", "all_tokens"])
 def test_part_maps_tiny(tiny, every):
     """The five indices are one chunk of tokens, the whole context (n = 16) two."""
@@ -201,18 +178,6 @@ def test_part_maps_refuses_a_process_group(tiny, monkeypatch):
     monkeypatch.setattr(optimize, "_world", lambda: (2, 0))
     with pytest.raises(ValueError, match="single process"):
         _part_maps(tiny, tiny[4])
-
-
-def _cli(folder, *extra):
-    from stablekeypoints_amd import main as cli
-    folder.mkdir()
-    g = torch.Generator().manual_seed(7)
-    torch.save(torch.randn(1, N_TOK, 32, generator=g), folder / "embedding.pt")
-    torch.save(torch.tensor([3, 7, 0, 12, 5]), folder / "indices.pt")
-    cli.main(["--model_type", "tiny", "--dataset_name", "synthetic", "--max_len", "5", "--num_tokens", str(N_TOK),
-              "--feature_upsample_res", str(R), "--augmentation_iterations", "2", "--start_from_stage", "predict",
-              "--save_folder", str(folder), "--device", DEV, *extra])
-    return torch.load(folder / "keypoints.pt", weights_only=True)
 
 
 def _part_files(folder, M, n, S):

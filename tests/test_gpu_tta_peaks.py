@@ -15,7 +15,7 @@ import torch
 import tta_peaks_ref
 import tta_ref
 import tta_tiny
-from tta_tiny import DEV, N_TOK, R, S_UP
+from tta_tiny import DEV, S_UP, cli as _cli, same_values as _same, tiny  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,13 +26,6 @@ NUMS = (1, 2, 3, 4)
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-
-
-def _same(a, b):
-    """Equal, with NaN in the same places."""
-    na, nb = torch.isnan(a), torch.isnan(b)
-    zero = torch.zeros((), device=a.device, dtype=a.dtype)
-    return a.shape == b.shape and torch.equal(na, nb) and torch.equal(torch.where(na, zero, a), torch.where(nb, zero, b))
 
 
 def _chain(avg, num, radius):
@@ -163,11 +156,6 @@ def test_tta_reduce_peaks_rejects_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def tiny():
-    return tta_tiny.build_tiny()
-
-
 def _predict(tiny, **kw):
     return tta_tiny.predict(tiny, tiny[2], augmentation_iterations=3, **kw)
 
@@ -201,23 +189,11 @@ def test_predict_keypoints_subjects_tiny(tiny):
 
 
 def test_cli_num_subjects_tiny(tmp_path):
-    from stablekeypoints_amd import main as cli
     names = ("subject_keypoints.pt", "subject_peak_values.pt", "subject_keypoints.csv")
-
-    def run(folder, *extra):
-        folder.mkdir()
-        g = torch.Generator().manual_seed(7)
-        torch.save(torch.randn(1, N_TOK, 32, generator=g), folder / "embedding.pt")
-        torch.save(torch.tensor([3, 7, 0, 12, 5]), folder / "indices.pt")
-        cli.main(["--model_type", "tiny", "--dataset_name", "synthetic", "--max_len", "5", "--num_tokens", str(N_TOK),
-                  "--feature_upsample_res", str(R), "--augmentation_iterations", "2", "--start_from_stage", "predict",
-                  "--save_folder", str(folder), "--device", DEV, *extra])
-        return torch.load(folder / "keypoints.pt", weights_only=True)
-
-    plain = run(tmp_path / "plain", "--num_subjects", "1")
+    plain = _cli(tmp_path / "plain", "--num_subjects", "1")
     assert not any((tmp_path / "plain" / f).exists() for f in names)
     out = tmp_path / "two"
-    kp = run(out, "--num_subjects", "2")
+    kp = _cli(out, "--num_subjects", "2")
     assert torch.equal(kp, plain)
     assert open(out / "keypoints.csv").read() == open(tmp_path / "plain" / "keypoints.csv").read()
     pos = torch.load(out / "subject_keypoints.pt", weights_only=True)

@@ -16,8 +16,7 @@ import torch
 
 import tta_ref
 import tta_score_ref
-import tta_tiny
-from tta_tiny import DEV, N_TOK, R, S_UP, predict as _predict, sequential as _sequential
+from tta_tiny import DEV, S_UP, cli as _cli, predict as _predict, sequential as _sequential, tiny  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -199,11 +198,6 @@ def test_tta_reduce_scored_rejects_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------ end to end
-@pytest.fixture(scope="module")
-def tiny():
-    return tta_tiny.build_tiny()
-
-
 def test_predict_keypoints_scores_tiny(tiny, monkeypatch):
     """kp and the maps are what they are without the scores.  The scores are those of
     ops.tta_reduce_scored on the pass's captured maps (recorded here as predict_keypoints calls
@@ -254,23 +248,11 @@ def test_predict_keypoints_scores_tiny(tiny, monkeypatch):
 
 
 def test_cli_keypoint_scores_tiny(tmp_path):
-    from stablekeypoints_amd import main as cli
     names = ("keypoint_scores.pt", "refined_keypoints.pt", "keypoint_scores.csv")
-
-    def run(folder, *extra):
-        folder.mkdir()
-        g = torch.Generator().manual_seed(7)
-        torch.save(torch.randn(1, N_TOK, 32, generator=g), folder / "embedding.pt")
-        torch.save(torch.tensor([3, 7, 0, 12, 5]), folder / "indices.pt")
-        cli.main(["--model_type", "tiny", "--dataset_name", "synthetic", "--max_len", "5", "--num_tokens", str(N_TOK),
-                  "--feature_upsample_res", str(R), "--augmentation_iterations", "2", "--start_from_stage", "predict",
-                  "--save_folder", str(folder), "--device", DEV, *extra])
-        return torch.load(folder / "keypoints.pt", weights_only=True)
-
-    plain = run(tmp_path / "plain")
+    plain = _cli(tmp_path / "plain")
     assert not any((tmp_path / "plain" / f).exists() for f in names)
     out = tmp_path / "scored"
-    kp = run(out, "--keypoint_scores")
+    kp = _cli(out, "--keypoint_scores")
     assert torch.equal(kp, plain)
     assert open(out / "keypoints.csv").read() == open(tmp_path / "plain" / "keypoints.csv").read()
     scores = torch.load(out / "keypoint_scores.pt", weights_only=True)

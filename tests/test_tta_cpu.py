@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import tta_abi
 import tta_ref
 
 
@@ -85,31 +86,32 @@ def test_ops_tta_reduce_refuses_cpu_tensors():
         ops.tta_reduce(torch.zeros(1, 1, 1, 4, 4), torch.zeros(1, 1, 2, 3))
 
 
-def test_tta_reduce_rejects_bad_arguments_without_gpu():
-    from stablekeypoints_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("libskp.so not built")
-    L = _lib.lib()
-    a = ctypes.c_void_p(256)   # aligned non-null dummy: every check below fails before any HIP call
-    ok = (a, 2, 3, 5, 37, a, a, None, a, None)
+@pytest.mark.parametrize("entry", list(tta_abi.ENTRY_POINTS))
+def test_every_tta_reduce_rejects_bad_common_arguments_without_gpu(entry):
+    """The checks that the five entry points share (check_common of skp_tta.hip), on each of them."""
+    L = tta_abi.library()
+    pointers = tta_abi.ENTRY_POINTS[entry][1]
 
     def rc_with(**kw):
-        args = list(ok)
-        for k, v in kw.items():
-            args[int(k[1:])] = v
-        return L.skp_tta_reduce(*args)
+        return tta_abi.rc_with(L, entry, **kw)
 
-    for slot in (0, 5, 6, 8):   # maps, theta_inv, pos, workspace
+    for slot in pointers:       # maps, theta_inv, pos, the query's further outputs, workspace
         assert rc_with(**{f"a{slot}": None}) == -1 and b"null" in L.skp_last_error()
     for slot in (1, 2, 3, 4):   # B, C, n, S
         for bad in (0, -1):
             assert rc_with(**{f"a{slot}": bad}) == -1 and b"non-positive" in L.skp_last_error()
     assert rc_with(a4=1) == -1 and b"at least 2" in L.skp_last_error()
-    assert rc_with(a8=ctypes.c_void_p(260)) == -1 and b"aligned" in L.skp_last_error()
+    assert rc_with(**{f"a{pointers[-1]}": ctypes.c_void_p(260)}) == -1 and b"aligned" in L.skp_last_error()
     # B·C·n·S² and the linear index must stay within int
-    assert L.skp_tta_reduce(a, 1, 1, 1, 46341, a, a, None, a, None) == -1 and b"2^31" in L.skp_last_error()
-    assert L.skp_tta_reduce(a, 8, 10, 10, 2048, a, a, None, a, None) == -1 and b"2^31" in L.skp_last_error()
-    # the workspace query: one (value, index) pair per image, token and 64 x 4-pixel tile
+    assert rc_with(a1=1, a2=1, a3=1, a4=46341) == -1 and b"2^31" in L.skp_last_error()
+    assert rc_with(a1=8, a2=10, a3=10, a4=2048) == -1 and b"2^31" in L.skp_last_error()
+    assert rc_with(a1=65536, a2=1, a3=1, a4=2) == -1 and b"65535 images" in L.skp_last_error()
+
+
+def test_tta_reduce_rejects_bad_arguments_without_gpu():
+    """The workspace query of skp_tta_reduce; its argument checks are the shared ones above."""
+    L = tta_abi.library()
+    # one (value, index) pair per image, token and 64 x 4-pixel tile
     assert L.skp_tta_reduce_workspace(1, 10, 512) == 10 * (8 * 128) * 8
     assert L.skp_tta_reduce_workspace(2, 5, 37) >= 2 * 5 * 8
     assert L.skp_tta_reduce_workspace(0, 1, 8) == -1 and L.skp_tta_reduce_workspace(1, 1, -3) == -1

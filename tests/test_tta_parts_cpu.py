@@ -2,13 +2,11 @@
 restatement tests/tta_parts_ref.py against torch on the CPU, the conditions its cases must keep
 meeting, the parser, the alias, the argument checks and the workspace size of skp_tta_reduce_parts
 through the C ABI, and eval.foreground_iou on hand-made arrays."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import tta_abi
 import tta_parts_ref
 import tta_ref
 from tta_parts_ref import CHUNKED_SHAPES, PARTS_SHAPES, parts_ref
@@ -129,37 +127,15 @@ def test_byte_model():
     assert ops.tta_reduce_parts_bytes(1, 2, 11, 8) == 4 * 2 * 11 * 64 + 10 * 64 + 20 * 2 * 64
 
 
-def _library():
-    from stablekeypoints_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("libskp.so not built")
-    return _lib.lib()
+_library = tta_abi.library
 
 
 def test_tta_reduce_parts_rejects_bad_arguments_without_gpu():
+    """The token bound and the workspace query; the checks every reduce shares are in tests/test_tta_cpu.py."""
     L = _library()
-    a = ctypes.c_void_p(256)   # aligned non-null dummy: every check below fails before any HIP call
-    #     maps B  C  n  S   theta pos label value mass avg   workspace stream
-    ok = (a, 2, 3, 5, 37, a, a, a, a, a, None, a, None)
-
-    def rc_with(**kw):
-        args = list(ok)
-        for k, v in kw.items():
-            args[int(k[1:])] = v
-        return L.skp_tta_reduce_parts(*args)
-
-    for slot in (0, 5, 6, 7, 8, 9, 11):   # maps, theta_inv, pos, label, value, mass, workspace
-        assert rc_with(**{f"a{slot}": None}) == -1 and b"null" in L.skp_last_error()
-    for slot in (1, 2, 3, 4):   # B, C, n, S
-        for bad in (0, -1):
-            assert rc_with(**{f"a{slot}": bad}) == -1 and b"non-positive" in L.skp_last_error()
-    assert rc_with(a4=1) == -1 and b"at least 2" in L.skp_last_error()
-    assert rc_with(a11=ctypes.c_void_p(260)) == -1 and b"aligned" in L.skp_last_error()
-    assert rc_with(a1=65536, a2=1, a3=1, a4=2) == -1 and b"65535 images" in L.skp_last_error()
-    assert rc_with(a1=1, a2=1, a3=1, a4=46341) == -1 and b"2^31" in L.skp_last_error()
-    assert rc_with(a1=8, a2=10, a3=10, a4=2048) == -1 and b"2^31" in L.skp_last_error()
     # the label is int16
-    assert rc_with(a1=1, a2=1, a3=32768, a4=2) == -1 and b"32767 tokens" in L.skp_last_error()
+    assert tta_abi.rc_with(L, "skp_tta_reduce_parts", a1=1, a2=1, a3=32768, a4=2) == -1
+    assert b"32767 tokens" in L.skp_last_error()
     assert L.skp_tta_reduce_parts_workspace(0, 1, 8) == -1 and L.skp_tta_reduce_parts_workspace(1, 1, -3) == -1
     assert L.skp_tta_reduce_parts_workspace(1, 0, 8) == -1 and L.skp_tta_reduce_parts_workspace(1, 1, 1) == -1
     # 2^31 bytes: 20 chunks of 4096² pixels are 10 · 20 · 2^24 bytes of partials

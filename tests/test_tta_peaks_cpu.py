@@ -1,14 +1,13 @@
 """CPU-side checks of the k-peak TTA reduce (no GPU needed): the numpy restatement
 tests/tta_peaks_ref.py against the numpy oracle, the planted cases through the float64 average, the
 parser and CLI, and the argument checks of skp_tta_reduce_peaks through the C ABI."""
-import ctypes
 import inspect
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import tta_abi
 import tta_peaks_ref
 import tta_ref
 
@@ -80,35 +79,13 @@ def test_ops_tta_reduce_peaks_refuses_cpu_tensors():
 
 
 def test_tta_reduce_peaks_rejects_bad_arguments_without_gpu():
-    from stablekeypoints_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("libskp.so not built")
-    L = _lib.lib()
-    a = ctypes.c_void_p(256)   # aligned non-null dummy: every check below fails before any HIP call
-    r2 = float(np.float32((0.05 * 37) ** 2))
-    #     maps B  C  n  S  theta num r2 pos values avg  ws stream
-    ok = (a, 2, 3, 5, 37, a, 3, r2, a, a, None, a, None)
-
-    def rc_with(**kw):
-        args = list(ok)
-        for k, v in kw.items():
-            args[int(k[1:])] = v
-        return L.skp_tta_reduce_peaks(*args)
-
-    for slot in (0, 5, 8, 9, 11):   # maps, theta_inv, pos, values, workspace
-        assert rc_with(**{f"a{slot}": None}) == -1 and b"null" in L.skp_last_error()
-    for slot in (1, 2, 3, 4):   # B, C, n, S
-        for bad in (0, -1):
-            assert rc_with(**{f"a{slot}": bad}) == -1 and b"non-positive" in L.skp_last_error()
-    assert rc_with(a4=1) == -1 and b"at least 2" in L.skp_last_error()
-    for bad in (0, 17, -1):
-        assert rc_with(a6=bad) == -1 and b"num" in L.skp_last_error()
-    for bad in (0.0, float("nan"), -1.0, float("inf")):
-        assert rc_with(a7=bad) == -1 and b"radius2" in L.skp_last_error()
-    assert rc_with(a11=ctypes.c_void_p(260)) == -1 and b"aligned" in L.skp_last_error()
-    # B·C·n·S² and the linear index must stay within int
-    assert rc_with(a1=1, a2=1, a3=1, a4=46341) == -1 and b"2^31" in L.skp_last_error()
-    assert rc_with(a1=8, a2=10, a3=10, a4=2048) == -1 and b"2^31" in L.skp_last_error()
+    """num, radius2 and the workspace query; the checks every reduce shares are in tests/test_tta_cpu.py."""
+    L = tta_abi.library()
+    r2 = tta_abi.R2
+    for bad in (0, 17, -1):                                 # slot 6 of skp_tta_reduce_peaks
+        assert tta_abi.rc_with(L, "skp_tta_reduce_peaks", a6=bad) == -1 and b"num" in L.skp_last_error()
+    for bad in (0.0, float("nan"), -1.0, float("inf")):     # slot 7
+        assert tta_abi.rc_with(L, "skp_tta_reduce_peaks", a7=bad) == -1 and b"radius2" in L.skp_last_error()
     # the workspace query: the partials of skp_tta_reduce and an index per image, token and round
     for B, n, S in ((1, 10, 512), (2, 5, 37), (1, 1, 2), (4, 10, 512)):
         for num in (1, 3, 16):

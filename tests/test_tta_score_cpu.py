@@ -1,13 +1,11 @@
 """CPU-side checks of the scored TTA reduce (no GPU needed): the float64 restatement
 tests/tta_score_ref.py against the numpy oracle, the parser, and the argument checks of
 skp_tta_reduce_scored through the C ABI."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import tta_abi
 import tta_ref
 import tta_score_ref
 
@@ -97,32 +95,10 @@ def test_keypoint_scores_fields():
 
 
 def test_tta_reduce_scored_rejects_bad_arguments_without_gpu():
-    from stablekeypoints_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("libskp.so not built")
-    L = _lib.lib()
-    a = ctypes.c_void_p(256)   # aligned non-null dummy: every check below fails before any HIP call
-    #     maps B  C  n  S  theta dist pos ref scores avg  ws stream
-    ok = (a, 2, 3, 5, 37, a, 5.0, a, a, a, None, a, None)
-
-    def rc_with(**kw):
-        args = list(ok)
-        for k, v in kw.items():
-            args[int(k[1:])] = v
-        return L.skp_tta_reduce_scored(*args)
-
-    for slot in (0, 5, 7, 8, 9, 11):   # maps, theta_inv, pos, refined, scores, workspace
-        assert rc_with(**{f"a{slot}": None}) == -1 and b"null" in L.skp_last_error()
-    for slot in (1, 2, 3, 4):   # B, C, n, S
-        for bad in (0, -1):
-            assert rc_with(**{f"a{slot}": bad}) == -1 and b"non-positive" in L.skp_last_error()
-    assert rc_with(a4=1) == -1 and b"at least 2" in L.skp_last_error()
-    assert rc_with(a11=ctypes.c_void_p(260)) == -1 and b"aligned" in L.skp_last_error()
-    for bad in (0.0, -1.0, 17.0, float("nan")):
-        assert rc_with(a6=bad) == -1 and b"distance" in L.skp_last_error()
-    # B·C·n·S² and the linear index must stay within int
-    assert rc_with(a1=1, a2=1, a3=1, a4=46341) == -1 and b"2^31" in L.skp_last_error()
-    assert rc_with(a1=8, a2=10, a3=10, a4=2048) == -1 and b"2^31" in L.skp_last_error()
+    """The distance and the workspace query; the checks every reduce shares are in tests/test_tta_cpu.py."""
+    L = tta_abi.library()
+    for bad in (0.0, -1.0, 17.0, float("nan")):     # slot 6 of skp_tta_reduce_scored
+        assert tta_abi.rc_with(L, "skp_tta_reduce_scored", a6=bad) == -1 and b"distance" in L.skp_last_error()
     # the workspace query: the partials of skp_tta_reduce, a double per tile, and the merged results
     for B, n, S in ((1, 10, 512), (2, 5, 37), (1, 1, 2), (4, 10, 512)):
         assert L.skp_tta_reduce_scored_workspace(B, n, S) >= L.skp_tta_reduce_workspace(B, n, S) > 0

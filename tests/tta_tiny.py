@@ -1,6 +1,8 @@
-"""What the GPU tests of the three TTA reduces share: the sequential composition of the existing
-ops that they are all held to, and the tiny model of their end-to-end tests with its seeded
-predict_keypoints call."""
+"""What the GPU tests of the TTA reduces share: the sequential composition of the existing ops that
+they are all held to, the bit comparisons, and the tiny model of their end-to-end tests with its
+seeded predict_keypoints, correspond_images and part_maps calls and its predict-stage CLI run."""
+import numpy as np
+import pytest
 import torch
 
 DEV = "cuda:0"
@@ -31,6 +33,25 @@ def sequential(maps, theta):
     return pos, avg, nums
 
 
+def bits(t):
+    """fp32 as its int32 bits (NaN compares as bits); any other dtype as it is."""
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def same_bits(got, want_np):
+    """A device tensor against a numpy array of the same dtype, bit for bit."""
+    got = got.cpu().numpy()
+    assert got.dtype == want_np.dtype and got.shape == want_np.shape
+    return np.array_equal(got.view(np.uint8), np.ascontiguousarray(want_np).view(np.uint8))
+
+
+def same_values(a, b):
+    """Two tensors equal, with NaN in the same places (whatever the NaNs' bits)."""
+    na, nb = torch.isnan(a), torch.isnan(b)
+    zero = torch.zeros((), device=a.device, dtype=a.dtype)
+    return a.shape == b.shape and torch.equal(na, nb) and torch.equal(torch.where(na, zero, a), torch.where(nb, zero, b))
+
+
 def build_tiny():
     """(ldm, controllers, two images, context, token indices) of the tiny model on DEV."""
     from stablekeypoints_amd import ptp_utils
@@ -45,6 +66,12 @@ def build_tiny():
     return ldm, {torch.device(DEV): ctl}, images, ctx, torch.tensor([3, 7, 0, 12, 5])
 
 
+@pytest.fixture(scope="module")
+def tiny():
+    """``build_tiny()`` once per test module that imports this fixture."""
+    return build_tiny()
+
+
 def seed():
     torch.manual_seed(123)
     torch.cuda.manual_seed(123)
@@ -57,3 +84,39 @@ def predict(tiny, images, **kw):
     seed()
     return ev.predict_keypoints(ldm, images, ctx, indices, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
                                 upscale_size=S_UP, **AUG, **kw)
+
+
+def correspond(tiny, **kw):
+    """correspond_images on the tiny model's two images from a fixed seed, both in one pass."""
+    from stablekeypoints_amd import eval as ev
+    ldm, controllers, images, ctx, _ = tiny
+    seed()
+    return ev.correspond_images(ldm, images, ctx, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
+                                upscale_size=S_UP, augmentation_iterations=3, image_batch=2, **AUG, **kw)
+
+
+def part_maps(tiny, indices, **kw):
+    """part_maps on the tiny model's two images from a fixed seed, both in one pass."""
+    from stablekeypoints_amd import eval as ev
+    ldm, controllers, images, ctx, _ = tiny
+    seed()
+    return ev.part_maps(ldm, images, ctx, indices, device=DEV, layers=[0, 1, 2, 3], controllers=controllers,
+                        upscale_size=S_UP, augmentation_iterations=3, image_batch=2, **AUG, **kw)
+
+
+INDICES = torch.tensor([3, 7, 0, 12, 5])
+
+
+def cli(folder, *extra, indices=INDICES):
+    """The CLI's predict stage on the tiny model and five synthetic images, from ``embedding.pt`` and (unless
+    ``indices`` is None) ``indices.pt`` written to ``folder`` -> the ``keypoints.pt`` it wrote."""
+    from stablekeypoints_amd import main
+    folder.mkdir(exist_ok=True)
+    g = torch.Generator().manual_seed(7)
+    torch.save(torch.randn(1, N_TOK, 32, generator=g), folder / "embedding.pt")
+    if indices is not None:
+        torch.save(indices, folder / "indices.pt")
+    main.main(["--model_type", "tiny", "--dataset_name", "synthetic", "--max_len", "5", "--num_tokens", str(N_TOK),
+               "--feature_upsample_res", str(R), "--augmentation_iterations", "2", "--start_from_stage", "predict",
+               "--save_folder", str(folder), "--device", DEV, *extra])
+    return torch.load(folder / "keypoints.pt", weights_only=True)
