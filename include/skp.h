@@ -587,6 +587,42 @@ int skp_tta_reduce_parts_workspace(int B, int n, int S);
 int skp_tta_reduce_parts(const float* maps, int B, int C, int n, int S, const float* theta_inv, float* pos,
                          short* label, float* value, float* mass, float* avg, void* workspace, void* stream);
 
+/* The match TTA reduce: skp_tta_reduce (eval.py:327-355, then eval.find_max_pixel, eval.py:39-60)
+ * and, in the same pass and without the average in memory, the combination ACROSS the tokens with the
+ * caller's weights: at every pixel the n averages are a signature, and each of Q query signatures is
+ * matched against every pixel by its cosine score (no reference function: few-shot transfer of
+ * annotated points).
+ *   pos, avg: skp_tta_reduce's, bit for bit.  queries (Q, n) row-major, 1 <= Q <= 16.  match_pos
+ *   (B, Q, 2), match_score (B, Q), score_map (B, Q, S, S) or NULL.
+ *   With a[b,t,p] the fp32 average of image b, token t and pixel p (after NaN -> 0) and d = queries:
+ *   nrm[b,p]     = Σ_t a·a,   dot[b,q,p] = Σ_t a·d[q,t],  both in this order: chunk k holds tokens
+ *                  10k … min(10k + 9, n−1); each chunk's sums start from 0.0f and add in token order;
+ *                  the chunks' sums are added in chunk order, again from 0.0f; every product and
+ *                  every add rounded on its own (no fma).  The part reduce's mass order.
+ *   score[b,q,p] = dot / sqrt(nrm), both correctly rounded; −inf where nrm is not > 0 (a pixel that
+ *                  no copy covers, an all-zero signature) and where the quotient is NaN (an infinite
+ *                  average): a score is never NaN, the order is total.
+ *   match_pos[b,q] = (row + 0.5, col + 0.5) of the first row-major maximum of score[b,q] over the S²
+ *                  pixels, match_score[b,q] that maximum; (0.5, 0.5) and −inf where every score is
+ *                  −inf.  score_map[b,q,p] = score[b,q,p] where it is given.
+ * Three or four launches, no atomics: the tile kernel (grid tiles × B × chunks of 10 tokens) leaves
+ * skp_tta_reduce's partials, and each thread carries its pixel's nrm and Q dots through its chunk's
+ * passes; with one chunk it forms the scores and the workgroup leaves one (score, pixel) partial per
+ * image, query and tile, with more it stores Q + 1 floats per image, chunk and pixel, and a
+ * per-pixel merge walks the chunks in order, forms the scores and leaves one partial per image,
+ * query and 64 pixels; then the merge for pos, and the same merge over the queries' partials.
+ * Deterministic, and the same whether or not score_map or avg is asked for.
+ * workspace: skp_tta_reduce_match_workspace(B, n, S, Q) bytes (−1 on a bad shape or Q, or at 2^31
+ * bytes), 8-B aligned: skp_tta_reduce's partials, with chunks = ⌈n / 10⌉ > 1 the (Q + 1)·B·chunks·S²
+ * floats, and two arrays of B·Q·R words, R = T tiles (one chunk) or ⌈S² / 64⌉, each array rounded
+ * up to 8 bytes: 8·B·n·T + [chunks > 1] r8(4(Q + 1)·B·chunks·S²) + 2·r8(4·B·Q·R).
+ * Rejected before any launch: what skp_tta_reduce rejects, a null queries, match_pos or
+ * match_score, Q outside [1, 16], more than 65535 chunks.                                       */
+int skp_tta_reduce_match_workspace(int B, int n, int S, int Q);
+int skp_tta_reduce_match(const float* maps, int B, int C, int n, int S, const float* theta_inv, const float* queries,
+                         int Q, float* pos, float* match_pos, float* match_score, float* score_map, float* avg,
+                         void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,8 @@ _SIGS = {
     "skp_tta_reduce_entropy": [_p, _c_int, _c_int, _c_int, _c_int, _p, _c_float, _p, _p, _p, _p, _p],
     "skp_tta_reduce_parts_workspace": [_c_int, _c_int, _c_int],
     "skp_tta_reduce_parts": [_p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p, _p, _p],
+    "skp_tta_reduce_match_workspace": [_c_int, _c_int, _c_int, _c_int],
+    "skp_tta_reduce_match": [_p, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p, _p, _p, _p, _p],
     "skp_version": [],
 }
 

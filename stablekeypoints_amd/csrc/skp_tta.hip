@@ -54,6 +54,18 @@
 // sum from 0.0f in token order and the chunks' sums from 0.0f in chunk order, so that the chunks can
 // run in different workgroups and give the same bits.  Two or three launches, no atomics.
 //
+// The match reduce (skp_tta_reduce_match) combines across the tokens with the caller's weights: at
+// every pixel the n averages are a signature, and for each of Q <= 16 query signatures the cosine
+// score dot / sqrt(nrm) with nrm = Σ_t a_t² and dot = Σ_t a_t·d[t], then the first row-major maximum
+// of each query's scores over the plane.  A thread owns its pixel, so nrm and the Q dots ride along
+// in registers through its chunk's passes (MatchCarry), the chunk's rows of the queries staged in
+// LDS.  The sums have the part reduce's mass order (each chunk from 0.0f in token order, the chunks
+// from 0.0f in chunk order, every product and sum rounded on its own).  With one chunk the tile
+// kernel forms the scores and leaves one (value, index) partial per (image, query, tile); with more
+// the threads store Q + 1 floats per (image, chunk, pixel) and a per-pixel merge walks the chunks in
+// order, forms the scores and leaves one partial per (image, query, 64 pixels).  tta_merge_kernel
+// reduces those as it reduces the tokens' partials.  Three or four launches, no atomics.
+//
 // Host side: layout() is the one statement of the workspace (the queries return its size, the entry
 // points take their pointers from its offsets), check_common() the checks the entry points
 // share, launch_tile() the tile kernel's launch.
@@ -220,22 +232,41 @@ struct PartsTileArgs : TileArgs {
   short* out_l;             // the lowest token of the chunk that attains it,
   float* out_m;             // and the chunk's sum (the outputs themselves where chunks == 1)
 };
-enum Tile { kTilePlain, kTileScored, kTileEntropy, kTileParts };
+constexpr int kMaxQueries = 16;
+struct MatchTileArgs : TileArgs {
+  const float* queries;     // (Q, n)
+  float* chunk;             // (B, chunks, Q + 1, S, S): the chunk's nrm, then its Q dots (chunks > 1)
+  float* score_map;         // (B, Q, S, S) or null      (chunks == 1: the tile kernel finishes the scores
+  float* qpart_v;           // (B, Q, tiles)              and leaves each query's partial of the tile)
+  int* qpart_i;
+  int Q;
+};
+// The match reduce's tile kernel is instantiated on a bucket of queries (4, 8 or 16 accumulators).
+enum Tile { kTilePlain, kTileScored, kTileEntropy, kTileParts, kTileMatch4, kTileMatch8, kTileMatch16 };
+constexpr int match_width(Tile K) { return K == kTileMatch4 ? 4 : K == kTileMatch8 ? 8 : K == kTileMatch16 ? 16 : 0; }
 template <Tile K>
 using ArgsOfTile = std::conditional_t<
-    K == kTileParts, PartsTileArgs,
-    std::conditional_t<K == kTileEntropy, EntropyTileArgs, TileArgsOf<K == kTileScored>>>;
+    match_width(K) != 0, MatchTileArgs,
+    std::conditional_t<K == kTileParts, PartsTileArgs,
+                       std::conditional_t<K == kTileEntropy, EntropyTileArgs, TileArgsOf<K == kTileScored>>>>;
 
 // What a thread of the part reduce carries through its chunk's passes: the greatest average so far
-// of its pixel, the lowest token that attains it and the sum so far.  The other reduces carry
-// nothing.
+// of its pixel, the lowest token that attains it and the sum so far.  A thread of the match reduce
+// carries its pixel's Σ a² and the QB dots so far; `rows` is the chunk's slice of the queries in LDS,
+// (kTok, QB) with zeros past Q.  The other reduces carry nothing.
 struct NoCarry {};
 struct Carry {
   float v, mass;
   int tok;
 };
+template <int QB>
+struct MatchCarry {
+  float nrm, dot[QB > 0 ? QB : 1];
+  const float4* rows;
+};
 template <Tile K>
-using CarryOf = std::conditional_t<K == kTileParts, Carry, NoCarry>;
+using CarryOf = std::conditional_t<match_width(K) != 0, MatchCarry<match_width(K)>,
+                                   std::conditional_t<K == kTileParts, Carry, NoCarry>>;
 // Token `tok`'s average `a` enters the carry: strict >, so the earlier token keeps a tie (a holds no
 // NaN: a total order); the add rounded on its own.
 __device__ __forceinline__ void carry_take(Carry& c, float a, int tok) {
@@ -245,6 +276,31 @@ __device__ __forceinline__ void carry_take(Carry& c, float a, int tok) {
     c.tok = tok;
   }
   c.mass = c.mass + a;
+}
+// The average `a` of the chunk's token `local` enters the match carry: nrm + a·a and, per query,
+// dot + a·d, every product and sum rounded on its own.  Four queries' weights come as one LDS read at
+// a wave-uniform address; a group of four past Q is skipped (uniform).
+template <int QB>
+__device__ __forceinline__ void match_take(MatchCarry<QB>& c, float a, int local, int Q) {
+#pragma clang fp contract(off)
+  const float sq = a * a;
+  c.nrm = c.nrm + sq;
+#pragma unroll
+  for (int g = 0; g < QB / 4; ++g)
+    if (4 * g < Q) {
+      const float4 d = c.rows[local * (QB / 4) + g];
+      const float p0 = a * d.x, p1 = a * d.y, p2 = a * d.z, p3 = a * d.w;
+      c.dot[4 * g] = c.dot[4 * g] + p0;
+      c.dot[4 * g + 1] = c.dot[4 * g + 1] + p1;
+      c.dot[4 * g + 2] = c.dot[4 * g + 2] + p2;
+      c.dot[4 * g + 3] = c.dot[4 * g + 3] + p3;
+    }
+}
+// The cosine score of a pixel: dot / sqrt(nrm), both correctly rounded (sqrt_rn: __fsqrt_rn is the
+// native approximation in this build); −inf where nrm is not > 0 and where the quotient is NaN.
+__device__ __forceinline__ float match_score(float dot, float nrm) {
+  const float s = __fdiv_rn(dot, sqrt_rn(nrm));
+  return (nrm > 0.0f && s == s) ? s : -INFINITY;
 }
 
 // Sums (s0, t) about the maximum m take in a partial (sk, tk) about mk <= m:
@@ -268,7 +324,7 @@ __device__ __forceinline__ void entropy_add(double& s0, double& t, float mk, dou
 // wave's maximum (the double exp; a pixel outside the plane or at −inf has e = 0, and e = 0 adds 0
 // to T), S0 and T through the wave tree into s_m[j] and s_m[kTok + j], then the four waves in order
 // about the tile's maximum.
-// kTileParts: each token's averaged value also enters the thread's carry, in token order.
+// kTileParts, kTileMatch*: each token's averaged value also enters the thread's carry, in token order.
 template <int NT, Tile K>
 __device__ __forceinline__ void tile_pass(const ArgsOfTile<K>& A, int t0, int b, int x, int y, bool inside, int p,
                                           float (*s_v)[kWaves], int (*s_i)[kWaves], double (*s_m)[kWaves],
@@ -307,6 +363,7 @@ __device__ __forceinline__ void tile_pass(const ArgsOfTile<K>& A, int t0, int b,
       a = a != a ? 0.0f : a;
       if (A.avg) A.avg[((size_t)b * A.n + t0 + j) * SS + p] = a;
       if constexpr (K == kTileParts) carry_take(carry, a, t0 + j);
+      if constexpr (match_width(K) != 0) match_take(carry, a, t0 + j - (int)blockIdx.z * kTok, A.Q);
       bv[j] = a;
       bi[j] = p;
     }
@@ -491,6 +548,134 @@ __global__ __launch_bounds__(WAVE) void tta_parts_merge_kernel(const float* __re
   mass[d] = m;
 }
 
+// The match reduce's tile kernel: the entropy reduce's grid (tiles_x · tiles_y, B, ⌈n / kTok⌉).  The
+// workgroup stages its chunk's rows of the queries in LDS, (kTok, QB) with zeros past Q and past the
+// chunk's last token; each thread carries its pixel's nrm and dots through the chunk's passes.  With
+// more than one chunk it stores them at (image, chunk, component, pixel) for tta_match_merge_kernel.
+// With one chunk (SINGLE; two instantiations, so that neither holds the other's pointers in SGPRs:
+// together they left a spill slot in the Q = 16 kernel's frame) it forms the Q scores itself, writes them where the score map is
+// asked for, and the workgroup leaves each query's best (score, pixel) of the tile: wave_best, then
+// the four waves as tile_pass combines them.  A thread outside the plane enters with (−inf, no index).
+template <int QB, bool SINGLE>
+__global__ __launch_bounds__(kThreads, 4) void tta_tile_match_kernel(const MatchTileArgs A) {
+  constexpr Tile K = QB == 4 ? kTileMatch4 : QB == 8 ? kTileMatch8 : kTileMatch16;
+  __shared__ float s_v[kTok][kWaves];
+  __shared__ int s_i[kTok][kWaves];
+  __shared__ double s_m[1][kWaves];
+  __shared__ float4 s_rows[kTok * (QB / 4)];
+  __shared__ float s_qv[QB][kWaves];
+  __shared__ int s_qi[QB][kWaves];
+  static_assert(kTok * QB <= kThreads, "one thread stages one weight");
+  const int b = blockIdx.y, tile = blockIdx.x, S = A.S, SS = S * S, Q = A.Q;
+  int x, y;
+  tile_pixel(tile % tiles_x(S), tile / tiles_x(S), x, y);
+  const bool inside = x < S && y < S;
+  const int p = inside ? y * S + x : 0;
+  const int t0 = blockIdx.z * kTok, t1 = min(t0 + kTok, A.n);
+  if (threadIdx.x < kTok * QB) {
+    const int j = threadIdx.x / QB, q = threadIdx.x % QB;
+    reinterpret_cast<float*>(s_rows)[threadIdx.x] = (q < Q && t0 + j < t1) ? A.queries[(size_t)q * A.n + t0 + j] : 0.0f;
+  }
+  __syncthreads();
+  MatchCarry<QB> carry;
+  carry.nrm = 0.0f;
+#pragma unroll
+  for (int q = 0; q < QB; ++q) carry.dot[q] = 0.0f;
+  carry.rows = s_rows;
+  tile_tokens<K>(A, t0, t1, b, x, y, inside, p, s_v, s_i, s_m, carry);
+  if constexpr (!SINGLE) {
+    if (inside) {
+      float* out = A.chunk + ((size_t)b * gridDim.z + blockIdx.z) * (Q + 1) * SS + p;
+      out[0] = carry.nrm;
+#pragma unroll
+      for (int q = 0; q < QB; ++q)
+        if (q < Q) out[(size_t)(q + 1) * SS] = carry.dot[q];
+    }
+    return;
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < QB; ++q)
+    if (q < Q) {   // uniform
+      float v = inside ? match_score(carry.dot[q], carry.nrm) : -INFINITY;
+      int i = inside ? p : kNoIndex;
+      if (A.score_map && inside) A.score_map[((size_t)b * Q + q) * SS + p] = v;
+      wave_best(v, i);
+      if (lane == 0) {
+        s_qv[q][wid] = v;
+        s_qi[q][wid] = i;
+      }
+    }
+  __syncthreads();
+  if (threadIdx.x < Q) {
+    const int q = threadIdx.x;
+    float v = s_qv[q][0];
+    int i = s_qi[q][0];
+#pragma unroll
+    for (int k = 1; k < kWaves; ++k)
+      if (better(s_qv[q][k], s_qi[q][k], v, i)) {
+        v = s_qv[q][k];
+        i = s_qi[q][k];
+      }
+    const size_t o = ((size_t)b * Q + q) * gridDim.x + blockIdx.x;
+    A.qpart_v[o] = v;
+    A.qpart_i[o] = i;
+  }
+}
+
+// The match reduce's merge over the chunks, grid (⌈S² / 64⌉, B, ⌈Q / 4⌉), one wave per workgroup as
+// tta_parts_merge_kernel: wave z takes its 64 pixels' nrm and the dots of queries 4z … 4z + 3, added
+// from 0.0f in chunk order, kAhead chunks' five values in flight together; then those queries'
+// scores, written where the score map is asked for, and each one's best (score, pixel) of the 64
+// pixels.  The waves of a pixel block each add nrm themselves, in the same order, hence to the same
+// bits: at Q = 16 that is 3/17 more loads for four times the waves and a quarter of the steps.  It
+// first took all Q + 1 values per wave, two chunks in flight: 38.2 µs for 50 chunks of 128² at
+// Q = 16, where the bytes are 9 µs.  Every lane stays to the end (wave_best needs the full wave): a
+// lane past the plane loads the last pixel's values and enters with (−inf, no index); a query past Q
+// loads the last query's and is not used.
+__global__ __launch_bounds__(WAVE) void tta_match_merge_kernel(const float* __restrict__ chunk, int chunks, int SS, int Q,
+                                                               float* __restrict__ score_map,
+                                                               float* __restrict__ qpart_v, int* __restrict__ qpart_i) {
+  constexpr int kAhead = 8, kGroup = 4;
+  const int p = blockIdx.x * WAVE + threadIdx.x, b = blockIdx.y, q0 = blockIdx.z * kGroup;
+  const bool inside = p < SS;
+  const float* in = chunk + (size_t)b * chunks * (Q + 1) * SS + min(p, SS - 1);
+  float nrm = 0.0f, dot[kGroup];
+#pragma unroll
+  for (int g = 0; g < kGroup; ++g) dot[g] = 0.0f;
+  for (int k0 = 0; k0 < chunks; k0 += kAhead) {
+    float vn[kAhead], vd[kAhead][kGroup];
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u) {
+      const float* at = in + (size_t)min(k0 + u, chunks - 1) * (Q + 1) * SS;   // past the last chunk: the last one again, not used
+      vn[u] = at[0];
+#pragma unroll
+      for (int g = 0; g < kGroup; ++g) vd[u][g] = at[(size_t)(1 + min(q0 + g, Q - 1)) * SS];
+    }
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u)
+      if (k0 + u < chunks) {
+        nrm = __fadd_rn(nrm, vn[u]);
+#pragma unroll
+        for (int g = 0; g < kGroup; ++g) dot[g] = __fadd_rn(dot[g], vd[u][g]);
+      }
+  }
+#pragma unroll
+  for (int g = 0; g < kGroup; ++g)
+    if (q0 + g < Q) {   // uniform
+      const int q = q0 + g;
+      float s = inside ? match_score(dot[g], nrm) : -INFINITY;
+      int i = inside ? p : kNoIndex;
+      if (score_map && inside) score_map[((size_t)b * Q + q) * SS + p] = s;
+      wave_best(s, i);
+      if (threadIdx.x == 0) {
+        const size_t o = ((size_t)b * Q + q) * gridDim.x + blockIdx.x;
+        qpart_v[o] = s;
+        qpart_i[o] = i;
+      }
+    }
+}
+
 // The merge of all three reduces, one wave per (image, token): the best of its `parts` partials
 // -> round `round`'s pos (row + 0.5, col + 0.5) at 2·(bt·num + round); plain and scored have num 1
 // and round 0.  The winning value goes to `value` (stride `value_stride`: the scores' first column,
@@ -507,7 +692,7 @@ __global__ __launch_bounds__(WAVE) void tta_parts_merge_kernel(const float* __re
 // values the lower index, a total order, so every variant's round 0 picks the same partial.  The
 // NaN-free reduction stays for kPlain and kScored because it is faster there: measured in their
 // place, the argmax-order merge took 8.3 µs against 6.9 µs (640 waves) and 9.1 against 7.8 (2560).
-enum Variant { kPlain, kScored, kPeaks, kEntropy, kParts };   // kParts: a layout only, its merge for pos is kPlain's
+enum Variant { kPlain, kScored, kPeaks, kEntropy, kParts, kMatch };   // kParts, kMatch: layouts only, their merges are kPlain's
 template <Variant V>
 __global__ __launch_bounds__(WAVE) void tta_merge_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i,
                                                          const double* __restrict__ part_m, int parts, int S, int num,
@@ -712,15 +897,21 @@ inline int mask_box(float radius2, int S) {
 //   part_m  P doubles (the tiles' S0), part_t  P doubles (their T)            (entropy)
 //   with chunks = ⌈n / kTok⌉ > 1 and Q = B·chunks·S²: cv  Q floats, cm  Q floats, cl  Q shorts,
 //   each rounded up to 8 bytes                                                (parts)
+//   with `num` = the queries, chunks = ⌈n / kTok⌉ and R = T (chunks == 1) or ⌈S² / 64⌉ partials per
+//   (image, query): chunk  (num + 1)·B·chunks·S² floats (chunks > 1 only), qpart_v  B·num·R floats,
+//   qpart_i  B·num·R ints, each rounded up to 8 bytes                         (match)
 // `bytes` is −1 for a shape no reduce takes (the queries' answer) and for 2^31 bytes or more.
 struct Layout {
-  long long part_v, part_i, part_m, part_t, total, peak_i, picks, cv, cm, cl;   // byte offsets; 0 where the variant has none
+  long long part_v, part_i, part_m, part_t, total, peak_i, picks, cv, cm, cl, chunk, qpart_v, qpart_i;   // byte offsets; 0 where the
+                                                                                         // variant has none
   long long bytes;
 };
 Layout layout(int B, int n, int S, Variant variant, int num) {
   Layout L = {};
   L.bytes = -1;
-  if (B <= 0 || n <= 0 || S < 2 || (variant == kPeaks && (num < 1 || num > kMaxPeaks))) return L;
+  if (B <= 0 || n <= 0 || S < 2 || (variant == kPeaks && (num < 1 || num > kMaxPeaks)) ||
+      (variant == kMatch && (num < 1 || num > kMaxQueries)))
+    return L;
   const long long bt = (long long)B * n, tiles = (long long)tiles_x(S) * tiles_y(S), big = 1ll << 28;
   if (bt >= big || tiles >= big || bt * tiles >= big) return L;   // 8·bt·tiles bytes of partials alone
   const long long parts = bt * tiles;
@@ -747,6 +938,14 @@ Layout layout(int B, int n, int S, Variant variant, int num) {
     L.cv = take((4 * Q + 7) & ~7ll);
     L.cm = take((4 * Q + 7) & ~7ll);
     L.cl = take((2 * Q + 7) & ~7ll);
+  }
+  if (variant == kMatch) {
+    const long long chunks = (n + kTok - 1) / kTok, SS = (long long)S * S;
+    // (num + 1)·B·chunks·S² <= 17·B·n·S² <= 17·256·parts < 2^41
+    if (chunks > 1) L.chunk = take((4 * (num + 1) * B * chunks * SS + 7) & ~7ll);
+    const long long R = chunks > 1 ? (SS + WAVE - 1) / WAVE : tiles;
+    L.qpart_v = take((4 * B * num * R + 7) & ~7ll);
+    L.qpart_i = take((4 * B * num * R + 7) & ~7ll);
   }
   if (end < (1ll << 31)) L.bytes = end;
   return L;
@@ -782,6 +981,23 @@ void launch_tile(const float* maps, int B, int C, int n, int S, const float* the
   if constexpr (SCORED) A.part_m = at<double>(workspace, L.part_m);
   A.C = C, A.n = n, A.S = S;
   hipLaunchKernelGGL(tta_tile_kernel<SCORED>, dim3(tiles_x(S) * tiles_y(S), B), dim3(kThreads), 0, st, A);
+}
+
+// The match reduce's tile kernel on its bucket of queries, grid (tiles, B, chunks), and with more than
+// one chunk the per-pixel merge over them (not launched where the tile kernel's launch failed: the
+// caller's check reports that error).
+template <int QB>
+void launch_match(const MatchTileArgs& A, int B, int chunks, hipStream_t st) {
+  const int S = A.S, SS = S * S;
+  const dim3 grid(tiles_x(S) * tiles_y(S), B, chunks);
+  if (chunks == 1) {
+    hipLaunchKernelGGL((tta_tile_match_kernel<QB, true>), grid, dim3(kThreads), 0, st, A);
+    return;
+  }
+  hipLaunchKernelGGL((tta_tile_match_kernel<QB, false>), grid, dim3(kThreads), 0, st, A);
+  if (hipPeekAtLastError() == hipSuccess)
+    hipLaunchKernelGGL(tta_match_merge_kernel, dim3((SS + WAVE - 1) / WAVE, B, (A.Q + 3) / 4), dim3(WAVE), 0, st, A.chunk,
+                       chunks, SS, A.Q, A.score_map, A.qpart_v, A.qpart_i);
 }
 
 }  // namespace
@@ -922,6 +1138,40 @@ extern "C" int skp_tta_reduce_parts(const float* maps, int B, int C, int n, int 
   }
   hipLaunchKernelGGL(tta_merge_kernel<kPlain>, dim3(B * n), dim3(WAVE), 0, st, A.part_v, A.part_i, nullptr, tiles, S, 1,
                      0, pos, nullptr, 0, nullptr, nullptr, nullptr, 0.0f);
+  SKP_LAUNCH_CHECK();
+  return SKP_OK;
+}
+
+extern "C" int skp_tta_reduce_match_workspace(int B, int n, int S, int Q) { return (int)layout(B, n, S, kMatch, Q).bytes; }
+
+extern "C" int skp_tta_reduce_match(const float* maps, int B, int C, int n, int S, const float* theta_inv,
+                                    const float* queries, int Q, float* pos, float* match_pos, float* match_score,
+                                    float* score_map, float* avg, void* workspace, void* stream) {
+  const int tiles = tiles_x(S) * tiles_y(S), chunks = (n + kTok - 1) / kTok;
+  const char* own = !(Q >= 1 && Q <= kMaxQueries) ? "Q must be in [1, 16]"
+                    : chunks > 65535              ? "more than 65535 chunks of tokens"
+                                                  : nullptr;
+  const Layout L = layout(B, n, S, kMatch, Q);
+  const char* bad = check_common(maps && theta_inv && queries && pos && match_pos && match_score && workspace, B, C, n, S,
+                                 own, L, workspace);
+  SKP_CHECK_ARG(!bad, bad);
+  MatchTileArgs A;
+  A.maps = maps, A.theta_inv = theta_inv, A.avg = avg;
+  A.part_v = at<float>(workspace, L.part_v), A.part_i = at<int>(workspace, L.part_i);
+  A.queries = queries, A.chunk = at<float>(workspace, L.chunk), A.score_map = score_map;
+  A.qpart_v = at<float>(workspace, L.qpart_v), A.qpart_i = at<int>(workspace, L.qpart_i);
+  A.C = C, A.n = n, A.S = S, A.Q = Q;
+  hipStream_t st = as_stream(stream);
+  if (Q <= 4) launch_match<4>(A, B, chunks, st);
+  else if (Q <= 8) launch_match<8>(A, B, chunks, st);
+  else launch_match<16>(A, B, chunks, st);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tta_merge_kernel<kPlain>, dim3(B * n), dim3(WAVE), 0, st, A.part_v, A.part_i, nullptr, tiles, S, 1,
+                     0, pos, nullptr, 0, nullptr, nullptr, nullptr, 0.0f);
+  SKP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tta_merge_kernel<kPlain>, dim3(B * Q), dim3(WAVE), 0, st, A.qpart_v, A.qpart_i, nullptr,
+                     chunks > 1 ? (S * S + WAVE - 1) / WAVE : tiles, S, 1, 0, match_pos, match_score, 1, nullptr, nullptr,
+                     nullptr, 0.0f);
   SKP_LAUNCH_CHECK();
   return SKP_OK;
 }

@@ -16,6 +16,10 @@ each average's argmax and softmax entropy from ``skp_tta_reduce_entropy``.
 ``part_maps`` (extra) says which of the chosen tokens owns each pixel of unlabelled images: per pixel
 the greatest of the tokens' TTA averages, the token that attains it and the tokens' sum from
 ``skp_tta_reduce_parts``; ``foreground_iou`` scores the labelled pixels against a foreground mask.
+``describe_points`` and ``transfer_keypoints`` (extra) carry points annotated on a few exemplar images
+over to unlabelled ones: at a pixel the tokens' TTA averages are a signature, an annotated pixel's
+signature is its landmark's descriptor, and ``skp_tta_reduce_match`` finds in every other image the
+pixel whose signature has the greatest cosine with it.
 """
 import collections
 import contextlib
@@ -247,7 +251,8 @@ def _images_per_pass(image_batch, pixels, C, n, S):
 
 def _tta_passes(name, ldm, images, context, indices, device, layers, noise_level, augment_degrees, augment_scale,
                 augment_translate, augmentation_iterations, controllers, upscale_size, image_batch):
-    """The capture passes of ``predict_keypoints``, ``correspond_images`` and ``part_maps`` (``name``
+    """The capture passes of ``predict_keypoints``, ``correspond_images``, ``part_maps``,
+    ``describe_points`` and ``transfer_keypoints`` (``name``
     is the caller's, for the messages).  ``images`` (M, 3, H, W) or (3, H, W) in [0, 1]; for image 0,
     then image 1, … C = ``augmentation_iterations`` thetas are drawn, each by one ``draw_theta(1)`` on
     the global CPU generator.  A pass warps the C copies of ``_images_per_pass`` whole images, captures
@@ -566,3 +571,124 @@ def foreground_iou(label, mask):
     inter = (fg & gt).flatten(1).sum(1).to(torch.float64)
     union = (fg | gt).flatten(1).sum(1).to(torch.float64)
     return torch.where(union > 0, inter / union.clamp_min(1.0), torch.ones_like(union))
+
+
+def _tokens_of(indices, context, C, S, what):
+    """``indices`` (default every token of ``context``) as (n,) int64 on the CPU, after the checks
+    ``part_maps`` makes of the shapes."""
+    if S < 2:
+        raise ValueError("upscale_size must be at least 2")
+    if indices is None:
+        indices = torch.arange(context.shape[-2])
+    indices = torch.as_tensor(indices, dtype=torch.int64).reshape(-1).cpu()
+    n = len(indices)
+    if n < 1:
+        raise ValueError("at least one token is needed")
+    if C * n * S * S >= 2 ** 31:
+        raise ValueError(f"one image's captured maps ({C} x {n} x {S} x {S}) reach 2^31 elements: {what} fewer "
+                         "tokens at a time or lower upscale_size")
+    return indices
+
+
+@torch.no_grad()
+def describe_points(ldm, images, points, context, indices=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
+                    noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
+                    augmentation_iterations=20, controllers=None, upscale_size=128, image_batch=None):
+    """Descriptors of landmarks annotated on a few exemplar images (extra: the captured maps are a
+    softmax over the tokens at every pixel, so the n tokens' TTA averages of eval.py:327-355 at a
+    pixel are a signature of what is there).
+
+    ``images`` is (K, 3, H, W) in [0, 1], the exemplars; ``points`` (K, Q, 2) holds landmark j's
+    (row, col) in [0, 1] on each of them, NaN where it is not annotated on that exemplar.  The
+    thetas are drawn as ``predict_keypoints`` draws them, every pass is captured for ``indices``
+    (token ids; default every token of ``context``) at ``upscale_size`` = S and reduced by
+    ``ops.tta_reduce(..., return_avg=True)`` (the exemplars are few: their averages may be in memory).
+    An annotation reads the pixel ``clamp(floor(point · S), 0, S − 1)``; the n averages there, in
+    float64, are scaled to unit length (a zero or non-finite vector contributes nothing).  A
+    landmark's descriptor is the sum of its exemplars' unit vectors in exemplar order, scaled to
+    unit length again.  Returns the (Q, n) float32 descriptors on ``device``, what
+    ``transfer_keypoints`` takes.  A landmark without any contribution raises ``ValueError``.
+    Single process only: under a process group of more than one rank it raises.
+    """
+    C, S = int(augmentation_iterations), int(upscale_size)
+    indices = _tokens_of(indices, context, C, S, "describe with")
+    pts = torch.as_tensor(points, dtype=torch.float64).cpu()
+    K = images.shape[0] if torch.as_tensor(images).dim() == 4 else 1
+    if pts.dim() != 3 or pts.shape[0] != K or pts.shape[2] != 2:
+        raise ValueError(f"points must be ({K}, Q, 2), got {tuple(pts.shape)}")
+    Q, n = pts.shape[1], len(indices)
+    if Q < 1:
+        raise ValueError("at least one landmark is needed")
+    annotated = ~torch.isnan(pts).any(dim=-1)                                   # (K, Q)
+    pixel = torch.nan_to_num(torch.floor(pts * S), nan=0.0).clamp(0, S - 1).long()
+    total = torch.zeros(Q, n, dtype=torch.float64)
+    for i0, nb, maps, th_inv in _tta_passes("describe_points", ldm, images, context, indices, device, layers,
+                                            noise_level, augment_degrees, augment_scale, augment_translate, C,
+                                            controllers, S, image_batch):
+        _, avg = ops.tta_reduce(maps, th_inv, return_avg=True)
+        del maps
+        for k in range(nb):             # exemplar order
+            rows, cols = pixel[i0 + k, :, 0].to(avg.device), pixel[i0 + k, :, 1].to(avg.device)
+            sig = avg[k][:, rows, cols].T.to(torch.float64).cpu()               # (Q, n)
+            length = (sig * sig).sum(dim=1).sqrt()
+            use = annotated[i0 + k] & torch.isfinite(length) & (length > 0)
+            unit = sig / torch.where(use, length, torch.ones_like(length))[:, None]
+            total += torch.where(use[:, None], unit, torch.zeros_like(unit))
+    length = (total * total).sum(dim=1).sqrt()
+    empty = [j for j in range(Q) if not (bool(torch.isfinite(length[j])) and float(length[j]) > 0)]
+    if empty:
+        raise ValueError(f"describe_points: landmark(s) {empty} have no descriptor: not annotated on any exemplar, "
+                         "or only at pixels whose signature is zero or not finite")
+    return (total / length[:, None]).to(torch.float32).to(device)
+
+
+Transferred = collections.namedtuple("Transferred", ["points", "score", "token_points", "score_maps"])
+MATCH_QUERIES = 16      # landmarks per ops.tta_reduce_match call
+
+
+@torch.no_grad()
+def transfer_keypoints(ldm, images, context, descriptors, indices=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
+                       noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
+                       augmentation_iterations=20, controllers=None, upscale_size=128, return_score_maps=False,
+                       image_batch=None):
+    """Where the landmarks of ``describe_points`` are in these unlabelled images (extra: few-shot
+    annotation transfer, without a regressor, a labelled set or the averages in memory).
+
+    ``images`` is (M, 3, H, W) in [0, 1]; ``descriptors`` (Q, n) are ``describe_points``' for the same
+    ``indices`` (token ids; default every token of ``context``) and ``upscale_size`` = S.  The thetas
+    are drawn as ``predict_keypoints`` draws them, and every pass is reduced by
+    ``ops.tta_reduce_match``: per image and landmark the pixel whose signature has the greatest
+    cosine with the descriptor.  More than 16 landmarks run in groups of 16, one call per group on
+    the same pass's maps.  Images per pass: what ``AUG_BATCH_PIXELS`` allows and what keeps the
+    captured maps below 2^31 elements, or ``image_batch``.
+
+    Returns ``Transferred(points, score, token_points, score_maps)``: ``points`` (M, Q, 2) the
+    landmarks' (row, col) = position / S, ``score`` (M, Q) their cosine (−inf where no pixel of the
+    image has a usable signature; the point is then (0.5, 0.5) / S), ``token_points`` (M, n, 2)
+    ``predict_keypoints``' points of those tokens, and ``score_maps`` (M, Q, S, S) every pixel's
+    score when ``return_score_maps``, else None.  Single process only: under a process group of more
+    than one rank it raises.
+    """
+    C, S = int(augmentation_iterations), int(upscale_size)
+    indices = _tokens_of(indices, context, C, S, "match")
+    n = len(indices)
+    desc = torch.as_tensor(descriptors, dtype=torch.float32)
+    if desc.dim() != 2 or desc.shape[0] < 1 or desc.shape[1] != n:
+        raise ValueError(f"descriptors must be (Q, {n}) with Q >= 1, got {tuple(desc.shape)}")
+    desc = desc.to(device).contiguous()
+    groups = [desc[g:g + MATCH_QUERIES] for g in range(0, desc.shape[0], MATCH_QUERIES)]
+    pos, points, scores, score_maps = [], [], [], []
+    for _, _, maps, th_inv in _tta_passes("transfer_keypoints", ldm, images, context, indices, device, layers,
+                                          noise_level, augment_degrees, augment_scale, augment_translate, C,
+                                          controllers, S, image_batch):
+        got = [ops.tta_reduce_match(maps, th_inv, d, return_scores=return_score_maps) for d in groups]
+        del maps
+        pos.append(got[0][0])
+        points.append(torch.cat([g[1] for g in got], dim=1))
+        scores.append(torch.cat([g[2] for g in got], dim=1))
+        if return_score_maps:
+            score_maps.append(torch.cat([g[3] for g in got], dim=1))
+    if not pos:
+        raise ValueError("at least one image is needed")
+    return Transferred(torch.cat(points) / S, torch.cat(scores), torch.cat(pos) / S,
+                       torch.cat(score_maps) if return_score_maps else None)

@@ -15,7 +15,11 @@ sharpest on the dataset's own images (``eval.correspond_images``: lowest summed 
 ``correspondences.png``), and predicts with those tokens; ``regressor.pt`` is then ignored.  With
 ``--part_maps`` it also writes which token owns each pixel of every image (``eval.part_maps`` at ``--part_size``:
 ``part_labels.pt`` (M, S, S) int16, −1 = background, ``part_mass.pt``, ``part_area.pt``, ``part_points.pt``, ``part_fg_iou.pt``
-where the dataset has foreground masks, and with ``--visualize`` ``parts.png``).  With ``--visualize``,
+where the dataset has foreground masks, and with ``--visualize`` ``parts.png``).  With ``--transfer K`` it also carries
+landmarks annotated on the dataset's first K images (``--transfer_points FILE``, or the items' own ``kpts``) over to every
+image (``eval.describe_points`` and ``eval.transfer_keypoints`` at ``--transfer_size``: ``transfer_descriptors.pt``,
+``transferred_keypoints.pt``, ``transfer_scores.pt``, ``transferred_keypoints.csv``, ``transfer_error.pt`` where the annotations
+are the dataset's, and with ``--visualize`` ``transfer.png``).  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -107,6 +111,17 @@ def build_parser():
                    help="--part_maps: label with the prediction's tokens, or with every token of embedding.pt")
     p.add_argument("--part_threshold", type=float, default=0.0,
                    help="--part_maps: a pixel whose tokens' attention sums to this or less is background")
+    p.add_argument("--transfer", type=int, default=None, metavar="K",
+                   help="predict stage only: the dataset's first K images are exemplars; the landmarks annotated on "
+                        "them are located in every image by the cosine of the tokens' TTA averages "
+                        "(transfer_descriptors.pt (Q, n), transferred_keypoints.pt (M, Q, 2), transfer_scores.pt (M, Q), "
+                        "transferred_keypoints.csv, and transfer_error.pt where the annotations are the dataset's kpts)")
+    p.add_argument("--transfer_points", type=str, default=None, metavar="FILE",
+                   help="--transfer: a saved (K, Q, 2) tensor of (row, col) in [0, 1], NaN where a landmark is not "
+                        "annotated on an exemplar; default: the exemplars' own kpts (visibility 0 = not annotated)")
+    p.add_argument("--transfer_size", type=int, default=128, help="--transfer: side S of the averages that are matched")
+    p.add_argument("--transfer_tokens", type=str, default="all", choices=["all", "indices"],
+                   help="--transfer: describe a pixel by every token of embedding.pt, or by the prediction's tokens")
     return p
 
 
@@ -239,6 +254,66 @@ def parts_stage(args, ldm, controllers, embedding, indices, dataset):
               f"{os.path.join(folder, 'part_labels.pt')}", flush=True)
 
 
+def transfer_stage(args, ldm, controllers, embedding, indices, dataset):
+    """``--transfer K``: the dataset's first K images are the exemplars.  Their annotations are
+    ``--transfer_points`` (a saved (K, Q, 2) tensor, (row, col) in [0, 1], NaN = not annotated) or the items' own
+    ``kpts`` (a landmark whose ``visibility`` is 0 counts as not annotated).  ``eval.describe_points`` turns them into
+    descriptors over every token of the embedding or (``--transfer_tokens indices``) the prediction's, at
+    ``--transfer_size``, and ``eval.transfer_keypoints`` locates them in every image of ``dataset``, the exemplars
+    included.  Writes ``transfer_descriptors.pt`` (Q, n), ``transferred_keypoints.pt`` (M, Q, 2), ``transfer_scores.pt``
+    (M, Q) and ``transferred_keypoints.csv`` (no header: index, file name where the reader has one, then per landmark
+    row, col, score); where the annotations came from ``kpts`` also ``transfer_error.pt`` (M, Q), the Euclidean distance
+    to the image's own annotation in normalised coordinates (NaN where the landmark is not visible), and prints its
+    mean over the non-exemplar images.  With ``--visualize`` ``transfer.png``: the first 12 images at most in one row,
+    landmark j in colour j.  The CPU and device RNG states are what they were on entry when it returns, so the
+    prediction that follows draws what a plain predict run draws."""
+    from .eval import describe_points, transfer_keypoints
+    folder, K, M = args.save_folder, int(args.transfer), len(dataset)
+    if not 1 <= K <= M:
+        raise ValueError(f"--transfer {K}: the exemplars are the dataset's first K images, and it has {M}")
+    with _rng_restored(args.device):
+        items = [dataset[i] for i in range(M)]
+        images = torch.stack([torch.as_tensor(it["img"]) for it in items])
+        own = args.transfer_points is None
+        if own:
+            if not all("kpts" in it for it in items):
+                raise ValueError("--transfer: the dataset's items carry no kpts; give --transfer_points")
+            kpts = torch.stack([torch.as_tensor(it["kpts"], dtype=torch.float32) for it in items])           # (M, Q, 2)
+            seen = torch.stack([torch.as_tensor(it["visibility"]) != 0 if "visibility" in it else
+                                torch.ones(kpts.shape[1], dtype=torch.bool) for it in items])                # (M, Q)
+            kpts = torch.where(seen[..., None], kpts, torch.full_like(kpts, float("nan")))
+            points = kpts[:K]
+        else:
+            points = torch.as_tensor(torch.load(args.transfer_points, weights_only=True), dtype=torch.float32)
+            if points.dim() != 3 or points.shape[0] != K or points.shape[2] != 2:
+                raise ValueError(f"--transfer_points must hold a ({K}, Q, 2) tensor, got {tuple(points.shape)}")
+        common = dict(indices=None if args.transfer_tokens == "all" else indices.cpu(), device=args.device,
+                      layers=args.layers, noise_level=args.noise_level, augment_degrees=args.augment_degrees,
+                      augment_scale=args.augment_scale, augment_translate=args.augment_translate,
+                      augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                      upscale_size=args.transfer_size)
+        desc = describe_points(ldm, images[:K], points, embedding, **common)
+        moved = transfer_keypoints(ldm, images, embedding, desc, **common)
+        pts, score = moved.points.cpu(), moved.score.cpu()
+        torch.save(desc.cpu(), os.path.join(folder, "transfer_descriptors.pt"))
+        torch.save(pts, os.path.join(folder, "transferred_keypoints.pt"))
+        torch.save(score, os.path.join(folder, "transfer_scores.pt"))
+        _write_rows(os.path.join(folder, "transferred_keypoints.csv"), _image_names(dataset),
+                    torch.cat([pts, score[..., None]], dim=-1))
+        if own:
+            error = (pts - kpts).pow(2).sum(dim=-1).sqrt()      # NaN where the landmark is not visible
+            torch.save(error, os.path.join(folder, "transfer_error.pt"))
+            rest = error[K:]
+            rest = rest[~torch.isnan(rest)]
+            mean = float(rest.mean()) if rest.numel() else float("nan")
+            print(f"transfer: mean distance to the annotations {mean:.4f} over {rest.numel()} visible landmarks of "
+                  f"{M - K} images", flush=True)
+        if args.visualize:
+            _save_row_sheet(os.path.join(folder, "transfer.png"), images, moved.points, args.device)
+        print(f"transfer: {K} exemplars, {desc.shape[0]} landmarks, {desc.shape[1]} tokens at {args.transfer_size} -> "
+              f"{os.path.join(folder, 'transferred_keypoints.pt')}", flush=True)
+
+
 def predict_stage(args, ldm, controllers, batch=4):
     """``--start_from_stage predict``: the keypoints of every image of the dataset (built as
     ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
@@ -256,7 +331,8 @@ def predict_stage(args, ldm, controllers, batch=4):
     With ``--correspond`` the indices come from ``correspond_stage`` on the same images, not from
     ``indices.pt``, and ``regressor.pt`` is not applied (it was fitted to other tokens).
     With ``--part_maps`` ``parts_stage`` first writes the part maps of the same images; the keypoints are
-    the same bits with and without it."""
+    the same bits with and without it.  With ``--transfer K`` ``transfer_stage`` does the same for the transferred
+    landmarks."""
     from .datasets import make_dataset
     from .eval import predict_keypoints
     folder = args.save_folder
@@ -274,6 +350,8 @@ def predict_stage(args, ldm, controllers, batch=4):
         regressor = _load(folder, "regressor.pt", args.device) if have_regressor else None
     if args.part_maps:
         parts_stage(args, ldm, controllers, embedding, indices, dataset)
+    if args.transfer is not None:
+        transfer_stage(args, ldm, controllers, embedding, indices, dataset)
     names = _image_names(dataset)
     k = int(args.num_subjects)
     kps, regs, scos, refs, pks, vals = [], [], [], [], [], []
@@ -341,6 +419,14 @@ def main(argv=None):
         parser.error("--part_maps belongs to --start_from_stage predict")
     if args.part_size < 2:
         parser.error("--part_size must be at least 2")
+    if args.transfer is None and args.transfer_points is not None:
+        parser.error("--transfer_points belongs to --transfer K")
+    if args.transfer is not None and args.start_from_stage != "predict":
+        parser.error("--transfer belongs to --start_from_stage predict")
+    if args.transfer is not None and args.transfer < 1:
+        parser.error("--transfer must be at least 1 (the number of exemplar images)")
+    if args.transfer_size < 2:
+        parser.error("--transfer_size must be at least 2")
     from .launch import launcher_env, spawn_ranks
     # torch.cuda.device_count() does not initialise HIP on this image, so the ranks can still start
     n = ranks_to_start(args, torch.cuda.device_count(), launcher_env())

@@ -2144,15 +2144,22 @@ def _tta_inputs(op, maps, theta_inv):
     return maps, _c(theta_inv.to(dev)), B, C, n, S, dev
 
 
-def _tta_workspace(op, dev, B, n, S, num=None, radius2=None):
-    """The cached workspace of ``skp_<op>``, sized by ``skp_<op>_workspace``; ``num`` and ``radius2``
-    are the k-peak query's further arguments (the size does not depend on ``radius2``)."""
-    key = (op, dev, B, n, S, num)
+# the first of a workspace query's further arguments, as the "bad shape" message names it
+_TTA_WS_ARG = {"tta_reduce_peaks": "num", "tta_reduce_match": "Q"}
+
+
+def _tta_workspace(op, dev, B, n, S, *args):
+    """The cached workspace of ``skp_<op>``, sized by ``skp_<op>_workspace(B, n, S, *args)``.  ``args``
+    are that query's further arguments in its order.  The size depends on the first of them alone
+    (``num`` of the k-peak query, not its ``radius2``; ``Q`` of the match query), so that one is part
+    of the cache's key."""
+    first = args[0] if args else None
+    key = (op, dev, B, n, S, first)
     ws = _TTA_WS.get(key)
     if ws is None:
-        nbytes = getattr(_lib.lib(), f"skp_{op}_workspace")(B, n, S, *(() if num is None else (num, radius2)))
+        nbytes = getattr(_lib.lib(), f"skp_{op}_workspace")(B, n, S, *args)
         if nbytes <= 0:
-            raise ValueError(f"{op}: bad shape B={B}, n={n}, S={S}" + ("" if num is None else f", num={num}"))
+            raise ValueError(f"{op}: bad shape B={B}, n={n}, S={S}" + (f", {_TTA_WS_ARG[op]}={first}" if args else ""))
         ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
     return ws
 
@@ -2160,17 +2167,19 @@ def _tta_workspace(op, dev, B, n, S, num=None, radius2=None):
 def _tta_call(op, maps, theta_inv, return_avg, query):
     """What the TTA reduces share around their one ``skp_<op>`` call.  After ``_tta_inputs``,
     ``query(B, C, n, S)`` checks the query's own arguments and returns ``(scalars, pos_shape, extras,
-    nbytes, ws_args)``: the scalars that ``skp_<op>`` takes after ``theta_inv``, the shape of ``pos``,
-    a ``(shape, dtype)`` per further output in the entry point's order, the byte model's value and the
-    workspace query's further arguments.  Returns ``(pos, *extras, avg)``: ``avg`` (B, n, S, S) when
-    ``return_avg``, else None."""
+    nbytes, ws_args)``: the arguments that ``skp_<op>`` takes after ``theta_inv`` (scalars, or
+    device tensors passed as pointers), the shape of ``pos``, a ``(shape, dtype)`` per further output
+    in the entry point's order (None for an optional output that is not asked for: a null pointer,
+    and None in the result), the byte model's value and the workspace query's further arguments.
+    Returns ``(pos, *extras, avg)``: ``avg`` (B, n, S, S) when ``return_avg``, else None."""
     maps, th, B, C, n, S, dev = _tta_inputs(op, maps, theta_inv)
     scalars, pos_shape, extras, nbytes, ws_args = query(B, C, n, S)
     ws = _tta_workspace(op, dev, B, n, S, *ws_args)
-    outs = [torch.empty(*shape, device=dev, dtype=dtype) for shape, dtype in [(pos_shape, F32), *extras]]
+    outs = [None if e is None else torch.empty(*e[0], device=dev, dtype=e[1]) for e in [(pos_shape, F32), *extras]]
     avg = torch.empty(B, n, S, S, device=dev, dtype=F32) if return_avg else None
+    own = [ptr(a) if torch.is_tensor(a) else a for a in scalars]   # `scalars` keeps its tensors alive
     with _timed(f"skp_{op}", nbytes):
-        call(f"skp_{op}", ptr(maps), B, C, n, S, ptr(th), *scalars, *map(ptr, outs), ptr(avg), ptr(ws), stream(dev))
+        call(f"skp_{op}", ptr(maps), B, C, n, S, ptr(th), *own, *map(ptr, outs), ptr(avg), ptr(ws), stream(dev))
     return (*outs, avg)
 
 
@@ -2309,3 +2318,45 @@ def tta_reduce_parts(maps, theta_inv, return_avg=False):
         return (), (B, n, 2), label_value_mass, tta_reduce_parts_bytes(B, C, n, S, return_avg), ()
 
     return _tta_call("tta_reduce_parts", maps, theta_inv, return_avg, query)
+
+
+def tta_reduce_match_bytes(B, C, n, S, Q, scores=False, avg=False):
+    """Byte model of skp_tta_reduce_match: ``tta_reduce_bytes`` plus the queries (4·Q·n), the matches
+    (12 bytes per image and query: a position and a score), with more than one chunk of 10 tokens the
+    Q + 1 floats per image, chunk and pixel written once and read once, and the score map where it is
+    asked for."""
+    chunks = (n + 9) // 10
+    return (tta_reduce_bytes(B, C, n, S, avg) + 4 * Q * n + 12 * B * Q
+            + (2 * 4 * (Q + 1) * B * chunks * S * S if chunks > 1 else 0) + (4 * B * Q * S * S if scores else 0))
+
+
+def tta_reduce_match(maps, theta_inv, queries, return_scores=False, return_avg=False):
+    """``tta_reduce`` with query signatures matched against every pixel (skp_tta_reduce_match).
+
+    At a pixel the n tokens' averages are a signature of what is there; ``queries`` (Q, n) float32 on
+    the maps' device holds Q of them, ``1 <= Q <= 16``.  Returns ``(pos, match_pos, match_score,
+    score_map, avg)``: ``pos`` and ``avg`` are ``tta_reduce``'s, bit for bit; ``match_pos`` (B, Q, 2)
+    is (row + 0.5, col + 0.5) of the first row-major maximum over the pixels of the cosine score
+    dot / sqrt(nrm), ``match_score`` (B, Q) that maximum, and ``score_map`` (B, Q, S, S) every score
+    when ``return_scores``, else None.  nrm = Σ_t a² and dot = Σ_t a·d in a fixed order (chunks of 10
+    tokens: each chunk's sums from 0 in token order, the chunks' sums from 0 in chunk order, no fma;
+    the plain sequential sums for n <= 10).  A score is −inf where nrm is not > 0 (a pixel that no copy
+    covers) or the quotient is NaN, never NaN; an image whose scores are all −inf gives (0.5, 0.5) and
+    −inf.  Neither the average nor the scores are in memory unless asked for.
+    """
+    _lib.require_device(queries)
+
+    def query(B, C, n, S):
+        if queries.dim() != 2 or queries.shape[1] != n or queries.dtype != F32:
+            raise ValueError(f"tta_reduce_match: queries must be (Q, {n}) float32, got {tuple(queries.shape)} "
+                             f"{queries.dtype}")
+        Q = queries.shape[0]
+        if not 1 <= Q <= 16:
+            raise ValueError(f"tta_reduce_match: Q must be in [1, 16], got {Q}")
+        if queries.device != maps.device:
+            raise ValueError(f"tta_reduce_match: queries on {queries.device}, maps on {maps.device}")
+        outs = [((B, Q, 2), F32), ((B, Q), F32), ((B, Q, S, S), F32) if return_scores else None]
+        nbytes = tta_reduce_match_bytes(B, C, n, S, Q, return_scores, return_avg)
+        return (_c(queries), Q), (B, n, 2), outs, nbytes, (Q,)
+
+    return _tta_call("tta_reduce_match", maps, theta_inv, return_avg, query)

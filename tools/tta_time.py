@@ -28,6 +28,11 @@ arithmetic; how far (b)'s double one-pass entropy is from it is recorded beside 
 tokens chunk by chunk in torch (one reduction over each chunk's 10 tokens, one over the chunks); whether
 (b)'s labels, values and positions equal (c)'s, and how far its mass is from (c)'s, is recorded beside the
 times.
+``match`` (Q = 16 unit queries) at the same four shapes, the same scheme: (b) skp_tta_reduce_match without the
+score map, (c) ops.tta_reduce(return_avg=True), then in torch the (Q × n)·(n × S²) product, the norm over the
+tokens, the division, the −inf rule and the argmax; whether (b)'s positions equal (c)'s and how far its
+scores are from (c)'s (torch sums in its own order) is recorded beside the times, and each row of the
+summary carries the byte model's floor and the share of the per-chunk sums in the maps' bytes.
 (a) is timed twice, before and after (b): the difference of its two medians is the run-to-run
 spread that (b) − (a), and (b) against (c), are read with.
 
@@ -35,7 +40,7 @@ Kernel times of ``scored`` and ``peaks`` come from a run of their own: under ``r
 --kernel-trace`` with ``--trace-only`` the subcommand only launches (a) and (b) a few times per
 shape (and num), and ``--kernel-trace FILE.csv`` folds that trace's per-kernel medians into the
 result.
-Usage: python tools/tta_time.py {reduce,scored,peaks,entropy,parts} [--out FILE.json] [--kernel-trace kernel_trace.csv]
+Usage: python tools/tta_time.py {reduce,scored,peaks,entropy,parts,match} [--out FILE.json] [--kernel-trace kernel_trace.csv]
        rocprofv3 --kernel-trace -d DIR -o tta --output-format csv -- python tools/tta_time.py scored --trace-only
 """
 import argparse
@@ -68,6 +73,9 @@ PEAKS_KERNELS = {"tta_masked_tile_kernel": "tta_masked_tile_kernel", "tta_merge_
 ENTROPY_KERNELS = {"tta_tile_entropy_kernel": "tile_entropy", "tta_merge_kernel<kEntropy>": "merge_entropy",
                    "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<false>": "tile_plain"}
 PARTS_KERNELS = {"tta_tile_parts_kernel": "tile_parts", "tta_parts_merge_kernel": "merge_parts",
+                 "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<false>": "tile_plain"}
+MATCH_QUERIES = 16
+MATCH_KERNELS = {"tta_tile_match_kernel": "tile_match", "tta_match_merge_kernel": "merge_match",
                  "tta_merge_kernel<kPlain>": "merge_plain", "tta_tile_kernel<false>": "tile_plain"}
 
 
@@ -118,14 +126,15 @@ def kernel_medians(path, names):
             name = row["Kernel_Name"]
             kernel = next((k for k in ("tta_window_kernel", "tta_masked_tile_kernel", "tta_merge_kernel",
                                        "tta_tile_kernel", "tta_tile_entropy_kernel", "tta_tile_parts_kernel",
-                                       "tta_parts_merge_kernel") if k in name), None)
+                                       "tta_parts_merge_kernel", "tta_tile_match_kernel", "tta_match_merge_kernel")
+                           if k in name), None)
             if kernel == "tta_tile_kernel":     # the template argument, demangled or mangled
                 kernel += "<true>" if ("<true>" in name or "ILb1" in name) else "<false>"
             elif kernel == "tta_merge_kernel":
                 kernel += "<" + ("kPlain", "kScored", "kPeaks", "kEntropy")[int(re.search(r"Variant\)?E?([0123])", name).group(1))] + ">"
             if kernel not in names:
                 continue
-            grid = "x".join(str(row.get(f"Grid_Size_{d}", "?")) for d in ("XYZ" if "entropy" in kernel or "parts" in kernel else "XY"))
+            grid = "x".join(str(row.get(f"Grid_Size_{d}", "?")) for d in ("XYZ" if "entropy" in kernel or "parts" in kernel or "match" in kernel else "XY"))
             by.setdefault(f"{names[kernel]}_grid{grid}", []).append(
                 (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
     return {k: dict(median_us=round(statistics.median(v), 2), launches=len(v)) for k, v in sorted(by.items())}
@@ -416,11 +425,80 @@ def run_parts(a):
                   summary=summary, rows=rows), PARTS_KERNELS)
 
 
+# ------------------------------------------------------------------------------------------ match
+def match_composition(maps, theta, queries):
+    """The outputs of tta_reduce_match from the ops that exist without it: the average written, then in
+    torch the queries' product with it, the norm over the tokens, the quotient, the −inf rule and the
+    first maximum of every (image, query)."""
+    B, C, n, S, _ = maps.shape
+    pos, avg = ops.tta_reduce(maps, theta, return_avg=True)
+    flat = avg.view(B, n, S * S)
+    dot = torch.matmul(queries, flat)
+    nrm = (flat * flat).sum(dim=1)
+    score = dot / nrm.sqrt()[:, None]
+    score = torch.where((nrm > 0)[:, None] & ~torch.isnan(score), score, torch.full_like(score, float("-inf")))
+    value, idx = score.max(dim=2)
+    return pos, torch.stack([idx // S + 0.5, idx % S + 0.5], dim=-1), value
+
+
+def run_match(a):
+    rows, summary = [], []
+    Q = MATCH_QUERIES
+    for (B, C, n, S), maps, theta, ws, pos in cases(PARTS_SHAPES):
+        wsm = torch.empty(lib().skp_tta_reduce_match_workspace(B, n, S, Q) // 8, device=DEV, dtype=torch.int64)
+        queries = torch.rand(Q, n, generator=torch.Generator().manual_seed(1)).to(DEV)
+        queries = (queries / queries.norm(dim=1, keepdim=True)).contiguous()
+        mpos, mscore = torch.empty(B, Q, 2, device=DEV), torch.empty(B, Q, device=DEV)
+
+        def plain():
+            call("skp_tta_reduce", ptr(maps), B, C, n, S, ptr(theta), ptr(pos), None, ptr(ws), stream(DEV))
+
+        def match():
+            call("skp_tta_reduce_match", ptr(maps), B, C, n, S, ptr(theta), ptr(queries), Q, ptr(pos), ptr(mpos),
+                 ptr(mscore), None, None, ptr(wsm), stream(DEV))
+
+        if a.trace_only:
+            trace(plain, match)
+            continue
+        # (c) moves the fused reduce with the average written, then reads the average twice (product, norm) and
+        # passes six times over the (B, Q, S²) scores (product out, quotient in and out, −inf rule in and out, max in)
+        comp_bytes = ops.tta_reduce_bytes(B, C, n, S, True) + 4 * B * n * S * S * 2 + 4 * B * Q * S * S * 6
+        fused_bytes = ops.tta_reduce_match_bytes(B, C, n, S, Q)
+        a_, spread, b_, c_ = a_b_a_c(a, rows, f"B{B}_C{C}_n{n}_S{S}", "skp_tta_reduce_match", plain, match,
+                                     lambda: match_composition(maps, theta, queries), ops.tta_reduce_bytes(B, C, n, S),
+                                     fused_bytes, comp_bytes)
+        got = ops.tta_reduce_match(maps, theta, queries)
+        want = match_composition(maps, theta, queries)
+        chunks = (n + 9) // 10
+        summary.append(dict(shape=[B, C, n, S], Q=Q, a_us=round(a_, 2), a_spread_us=round(spread, 2), b_us=round(b_, 2),
+                            c_us=round(c_, 2), b_minus_a_us=round(b_ - a_, 2), b_over_a=round(b_ / a_, 3),
+                            b_over_c=round(b_ / c_, 3), b_below_c_by_more_than_spread=bool(b_ < c_ - spread),
+                            b_floor_us=round(fused_bytes / COPY_RATE * 1e6, 2),
+                            b_over_floor=round(b_ / (fused_bytes / COPY_RATE * 1e6), 2),
+                            chunk_sums_share_of_maps_bytes_each_way=round(
+                                (Q + 1) * chunks / (C * n) if chunks > 1 else 0.0, 4),
+                            pos_agree=bool(torch.equal(got[0], want[0])),
+                            match_pos_agree=float((got[1] == want[1]).all(dim=-1).float().mean()),
+                            match_score_max_abs_vs_torch_order=float((got[2] - want[2]).abs().max())))
+        print(json.dumps(summary[-1]), flush=True)
+    if a.trace_only:
+        return
+    write(a, dict(device=torch.cuda.get_device_name(0), warmup=a.warmup, iters=a.iters, copy_rate_Bps=COPY_RATE,
+                  note="median of iters, launches between two HIP events; a = skp_tta_reduce (the lower of two medians, "
+                       "their difference = a_spread), b = skp_tta_reduce_match with Q = 16 queries and no score map, c = "
+                       "the composition ops.tta_reduce(return_avg=True) + matmul, norm, quotient, -inf rule and max in "
+                       "torch (host time between its launches included); no average written by a or b; b_floor = "
+                       "ops.tta_reduce_match_bytes at the copy rate; match_pos_agree = the share of (image, query) "
+                       "pairs whose position equals the composition's (torch sums in its own order); kernels = "
+                       "per-kernel medians of a kernel trace taken in a run of its own",
+                  summary=summary, rows=rows), MATCH_KERNELS)
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="which", required=True)
     for name, run in (("reduce", run_reduce), ("scored", run_scored), ("peaks", run_peaks), ("entropy", run_entropy),
-                      ("parts", run_parts)):
+                      ("parts", run_parts), ("match", run_match)):
         p = sub.add_parser(name)
         p.set_defaults(run=run)
         p.add_argument("--out", default=None)
