@@ -623,6 +623,33 @@ int skp_tta_reduce_match(const float* maps, int B, int C, int n, int S, const fl
                          int Q, float* pos, float* match_pos, float* match_score, float* score_map, float* avg,
                          void* workspace, void* stream);
 
+/* The dense nearest-pixel field (no reference function: transfer of everything an exemplar carries):
+ * for every pixel p of X the pixel q of Y whose signature has the greatest cosine, on the exact-f32
+ * matrix cores, the (P, Q) product never leaving registers.
+ *   x: image b's signatures at x + b·x_stride, token-major (n, P): element (t, p) at t·P + p, an
+ *   (n, S, S) TTA average as it lies in memory; a stride of 0 is one operand shared by the B images.
+ *   y likewise with Q columns.  index (B, P) int32, score (B, P) float32.
+ *   Per image, every operation fp32 and rounded on its own:
+ *   nx[p]     = c_n with c_0 = 0.0f, c_{t+1} = fmaf(x[t,p], x[t,p], c_t); ny[q] likewise.  A column is
+ *               usable where 0 < norm < +inf (not a zero column, nor one holding a NaN or an infinity).
+ *   rx[p]     = 1.0f / sqrt(nx[p]), both correctly rounded; ry[q] likewise.
+ *   dot[p,q]  = d_n with d_0 = 0.0f, d_{t+1} = fmaf(x[t,p], y[t,q], d_t), in token order: one
+ *               accumulator per (p, q), no split over the tokens.
+ *   key[p,q]  = dot · ry[q]; a NaN key counts as −inf.
+ *   index[p]  = the lowest usable q with the greatest key, for a usable p;
+ *   score[p]  = key[p,index[p]] · rx[p];  index = −1 and score = −inf where p is not usable or no q is.
+ * A key depends neither on the tile of p or q, nor on the split of Q, nor on the image's place in the
+ * batch.  Two launches, no atomics: the field kernel (one workgroup per image, 128 p and split of Q;
+ * it forms the norms from the panels it streams and leaves one (key, q) partial per p) and the merge
+ * over the splits in split order (the greater key wins, on equal keys the lower q).
+ * workspace: skp_match_field_workspace(B, n, P, Q) bytes (−1 on a bad shape, or at 2^31 bytes), 8-B
+ * aligned: r8(4·B·P) + 2·r8(4·B·splits·P) with splits <= 32 — never of the order of P·Q.
+ * Rejected before any launch: a null pointer; B, n, P or Q below 1; n > 4096; P or Q above 2^20; a
+ * non-zero stride below n·P or n·Q.                                                             */
+int skp_match_field_workspace(int B, int n, int P, int Q);
+int skp_match_field(const float* x, long long x_stride, int P, const float* y, long long y_stride, int Q, int B,
+                    int n, int* index, float* score, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

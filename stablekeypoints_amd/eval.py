@@ -20,6 +20,9 @@ the greatest of the tokens' TTA averages, the token that attains it and the toke
 over to unlabelled ones: at a pixel the tokens' TTA averages are a signature, an annotated pixel's
 signature is its landmark's descriptor, and ``skp_tta_reduce_match`` finds in every other image the
 pixel whose signature has the greatest cosine with it.
+``match_images`` (extra) matches EVERY pixel of unlabelled images against a source image and back
+(``skp_match_field``, the (S², S²) product never in memory); ``transfer_labels`` and
+``transfer_points_dense`` read masks, part segmentations and any number of points off that field.
 """
 import collections
 import contextlib
@@ -692,3 +695,124 @@ def transfer_keypoints(ldm, images, context, descriptors, indices=None, device="
         raise ValueError("at least one image is needed")
     return Transferred(torch.cat(points) / S, torch.cat(scores), torch.cat(pos) / S,
                        torch.cat(score_maps) if return_score_maps else None)
+
+
+DenseMatch = collections.namedtuple("DenseMatch", ["index", "score", "back_index", "back_score", "cycle",
+                                                   "token_points"])
+
+
+def _cycle_distance(index, back_index, S):
+    """(M, S²) forward and backward fields -> (M, S²) float32 distance in pixels between p and
+    ``back_index[index[p]]``, +inf where either index is −1."""
+    hop = torch.gather(back_index.long(), 1, index.long().clamp_min(0))
+    p = torch.arange(S * S, device=index.device)[None]
+    dr, dc = p // S - hop.clamp_min(0) // S, p % S - hop.clamp_min(0) % S
+    dist = (dr * dr + dc * dc).to(torch.float64).sqrt().to(torch.float32)
+    return dist.masked_fill((index < 0) | (hop < 0), float("inf"))
+
+
+@torch.no_grad()
+def match_images(ldm, source, images, context, indices=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
+                 noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
+                 augmentation_iterations=20, controllers=None, upscale_size=128, image_batch=None):
+    """The dense field between one source image and unlabelled images (extra: everything an exemplar
+    carries — a mask, a part segmentation, any number of points — transfers through one operation: for
+    every pixel of one image the pixel of the other whose signature, the n tokens' TTA averages, has
+    the greatest cosine).
+
+    ``source`` is (3, H, W) and ``images`` (M, 3, H, W), in [0, 1].  The source's
+    ``augmentation_iterations`` thetas are drawn first, then the images' as ``predict_keypoints`` draws
+    them; every pass is reduced by ``ops.tta_reduce(..., return_avg=True)`` and the source's averages
+    are kept for the whole call.  Per pass two ``ops.match_field`` calls: the images' pixels against
+    the source's, and the source's pixels against each image's.
+
+    Returns ``DenseMatch(index, score, back_index, back_score, cycle, token_points)``, the first five
+    (M, S, S) with S = ``upscale_size``: ``index`` int32 the source pixel (row · S + col) matched to
+    each image pixel and ``score`` its cosine, −1 and −inf where the pixel's signature is not usable
+    (a pixel no copy covers) or no source pixel's is; ``back_index`` / ``back_score`` the image pixel
+    matched to each SOURCE pixel; ``cycle`` float32 the distance in pixels between p and
+    ``back_index[index[p]]``, +inf where either index is −1; ``token_points`` (M, n, 2)
+    ``predict_keypoints``' points of those tokens.  Single process only: under a process group of
+    more than one rank it raises.
+    """
+    C, S = int(augmentation_iterations), int(upscale_size)
+    indices = _tokens_of(indices, context, C, S, "match")
+    n = len(indices)
+    src = torch.as_tensor(source)
+    if src.dim() != 3 or src.shape[0] != 3:
+        raise ValueError(f"source must be (3, H, W), got {tuple(src.shape)}")
+    common = (noise_level, augment_degrees, augment_scale, augment_translate, C, controllers, S)
+    src_avg = None
+    for _, _, maps, th_inv in _tta_passes("match_images", ldm, src, context, indices, device, layers, *common, 1):
+        _, src_avg = ops.tta_reduce(maps, th_inv, return_avg=True)
+        del maps
+    src_sig = src_avg.reshape(1, n, S * S)
+    pos, fields = [], ([], [], [], [])
+    for _, nb, maps, th_inv in _tta_passes("match_images", ldm, images, context, indices, device, layers, *common,
+                                           image_batch):
+        p, avg = ops.tta_reduce(maps, th_inv, return_avg=True)
+        del maps
+        sig = avg.reshape(nb, n, S * S)
+        got = ops.match_field(sig, src_sig) + ops.match_field(src_sig, sig)
+        del avg, sig
+        pos.append(p)
+        for acc, t in zip(fields, got):
+            acc.append(t)
+    if not pos:
+        raise ValueError("at least one image is needed")
+    index, score, back_index, back_score = (torch.cat(f) for f in fields)
+    M = index.shape[0]
+    cycle = _cycle_distance(index, back_index, S)
+    return DenseMatch(*(t.reshape(M, S, S) for t in (index, score, back_index, back_score, cycle)),
+                      torch.cat(pos) / S)
+
+
+def transfer_labels(match, labels, max_cycle=None, min_score=None):
+    """The source's labels carried to every image of a ``DenseMatch``.
+
+    ``labels`` is (S, S) integer on the source's grid, −1 for unlabelled and at most 32767.  Returns
+    (M, S, S) int16: the label of the matched source pixel, and −1 where ``index`` is −1, where
+    ``cycle > max_cycle`` or where ``score < min_score`` (each gate only where it is given).
+    """
+    index = torch.as_tensor(match.index)
+    M, S = index.shape[0], index.shape[-1]
+    lab = torch.as_tensor(labels)
+    if lab.is_floating_point() or lab.dtype == torch.bool or tuple(lab.shape) != (S, S):
+        raise ValueError(f"labels must be ({S}, {S}) integer, got {tuple(lab.shape)} {lab.dtype}")
+    if lab.numel() and (int(lab.min()) < -1 or int(lab.max()) > 32767):
+        raise ValueError("labels must lie in [-1, 32767]")
+    lab = lab.to(index.device, torch.int16).reshape(-1)
+    keep = index >= 0
+    if max_cycle is not None:
+        keep &= ~(torch.as_tensor(match.cycle).to(index.device) > float(max_cycle))
+    if min_score is not None:
+        keep &= ~(torch.as_tensor(match.score).to(index.device) < float(min_score))
+    out = lab[index.long().clamp_min(0).reshape(-1)].reshape(M, S, S)
+    return torch.where(keep, out, torch.full_like(out, -1))
+
+
+def transfer_points_dense(match, points):
+    """Points annotated on the source, read off a ``DenseMatch``'s backward field.
+
+    ``points`` is (Q, 2) (row, col) in [0, 1] on the source, NaN where not annotated; Q is not
+    limited.  A point reads the source pixel ``clamp(floor(point · S), 0, S − 1)``.  Returns
+    ``(positions (M, Q, 2), scores (M, Q))``: the matched image pixel's (row, col) / S and its cosine
+    from ``back_index`` and ``back_score``; NaN and −inf for a NaN point, and for a source pixel
+    without a match (``back_index`` −1).
+    """
+    back = torch.as_tensor(match.back_index)
+    M, S = back.shape[0], back.shape[-1]
+    dev = back.device
+    pts = torch.as_tensor(points, dtype=torch.float64)
+    if pts.dim() != 2 or pts.shape[1] != 2:
+        raise ValueError(f"points must be (Q, 2), got {tuple(pts.shape)}")
+    pts = pts.to(dev)
+    annotated = ~torch.isnan(pts).any(dim=-1)
+    pixel = torch.nan_to_num(torch.floor(pts * S), nan=0.0).clamp(0, S - 1).long()
+    flat = pixel[:, 0] * S + pixel[:, 1]                                          # (Q,)
+    hit = back.reshape(M, S * S)[:, flat].long()                                  # (M, Q)
+    sc = torch.as_tensor(match.back_score).to(dev).reshape(M, S * S)[:, flat]
+    ok = annotated[None] & (hit >= 0)
+    pos = torch.stack([hit.clamp_min(0) // S, hit.clamp_min(0) % S], dim=-1).to(torch.float32) / S
+    pos = torch.where(ok[..., None], pos, torch.full_like(pos, float("nan")))
+    return pos, torch.where(ok, sc, torch.full_like(sc, float("-inf")))

@@ -19,7 +19,10 @@ where the dataset has foreground masks, and with ``--visualize`` ``parts.png``).
 landmarks annotated on the dataset's first K images (``--transfer_points FILE``, or the items' own ``kpts``) over to every
 image (``eval.describe_points`` and ``eval.transfer_keypoints`` at ``--transfer_size``: ``transfer_descriptors.pt``,
 ``transferred_keypoints.pt``, ``transfer_scores.pt``, ``transferred_keypoints.csv``, ``transfer_error.pt`` where the annotations
-are the dataset's, and with ``--visualize`` ``transfer.png``).  With ``--visualize``,
+are the dataset's, and with ``--visualize`` ``transfer.png``).  With ``--dense_transfer SRC`` it also matches every pixel of
+every image against the dataset's first image and carries that image's labels over (``eval.match_images`` and
+``eval.transfer_labels`` at ``--dense_size``: ``dense_index.pt``, ``dense_score.pt``, ``dense_cycle.pt``, ``dense_labels.pt``,
+``dense_fg_iou.pt`` where the dataset has foreground masks, and with ``--visualize`` ``dense.png``).  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -122,6 +125,20 @@ def build_parser():
     p.add_argument("--transfer_size", type=int, default=128, help="--transfer: side S of the averages that are matched")
     p.add_argument("--transfer_tokens", type=str, default="all", choices=["all", "indices"],
                    help="--transfer: describe a pixel by every token of embedding.pt, or by the prediction's tokens")
+    p.add_argument("--dense_transfer", type=str, default=None, metavar="SRC",
+                   help="predict stage only: the dataset's first image is the source; every pixel of every image is matched "
+                        "to the source pixel whose tokens' TTA averages have the greatest cosine, and the source's labels "
+                        "are carried over (dense_index.pt, dense_score.pt, dense_cycle.pt (M, S, S), dense_labels.pt (M, S, S) "
+                        "int16, and dense_fg_iou.pt where the dataset has foreground masks).  SRC: 'mask' (the first item's "
+                        "mask: foreground 0, background -1) or a saved integer tensor of labels for the source, -1 = "
+                        "unlabelled, nearest-resized to --dense_size")
+    p.add_argument("--dense_size", type=int, default=128, help="--dense_transfer: side S of the averages that are matched")
+    p.add_argument("--dense_tokens", type=str, default="all", choices=["all", "indices"],
+                   help="--dense_transfer: describe a pixel by every token of embedding.pt, or by the prediction's tokens")
+    p.add_argument("--dense_max_cycle", type=float, default=None,
+                   help="--dense_transfer: no label where the match does not come back within this many pixels")
+    p.add_argument("--dense_min_score", type=float, default=None,
+                   help="--dense_transfer: no label where the match's cosine is below this")
     return p
 
 
@@ -314,6 +331,73 @@ def transfer_stage(args, ldm, controllers, embedding, indices, dataset):
               f"{os.path.join(folder, 'transferred_keypoints.pt')}", flush=True)
 
 
+def dense_stage(args, ldm, controllers, embedding, indices, dataset):
+    """``--dense_transfer SRC``: the dataset's first image is the source.  ``eval.match_images`` matches every
+    pixel of every image of ``dataset`` (the source included) against it and back at ``--dense_size`` = S, over
+    every token of the embedding or (``--dense_tokens indices``) the prediction's; ``eval.transfer_labels`` carries
+    the source's labels over, gated by ``--dense_max_cycle`` and ``--dense_min_score`` where given.  The labels are
+    ``SRC``: ``mask`` (the first item's ``mask``: foreground 0, background −1) or a saved integer tensor for the
+    source (−1 = unlabelled), either nearest-resized to (S, S).  Writes ``dense_index.pt`` (M, S, S) int32,
+    ``dense_score.pt`` and ``dense_cycle.pt`` (M, S, S) float32 and ``dense_labels.pt`` (M, S, S) int16; where the
+    dataset's items carry ``mask`` also ``dense_fg_iou.pt`` (M,) float64, ``eval.foreground_iou`` of the transferred
+    labels, and prints its mean over the non-source images.  With ``--visualize`` ``dense.png``, tinted as
+    ``parts.png`` is.  The CPU and device RNG states are what they were on entry when it returns, so the prediction
+    that follows draws what a plain predict run draws."""
+    from . import ops
+    from .eval import foreground_iou, match_images, transfer_labels
+    folder, S, M = args.save_folder, int(args.dense_size), len(dataset)
+    if M < 1:
+        raise ValueError("--dense_transfer: the dataset is empty")
+    with _rng_restored(args.device):
+        items = [dataset[i] for i in range(M)]
+        images = torch.stack([torch.as_tensor(it["img"]) for it in items])
+        have_masks = all("mask" in it for it in items)
+        if args.dense_transfer == "mask":
+            if "mask" not in items[0]:
+                raise ValueError("--dense_transfer mask: the dataset's items carry no mask; give a file of labels")
+            mask = torch.as_tensor(items[0]["mask"], dtype=torch.float32)
+            mask = mask[..., 0] if mask.dim() == 3 and mask.shape[-1] == 1 else mask
+            labels = torch.where(mask > 0.5, 0, -1)
+        else:
+            labels = torch.as_tensor(torch.load(args.dense_transfer, weights_only=True))
+            if labels.dim() != 2 or labels.is_floating_point() or labels.dtype == torch.bool:
+                raise ValueError(f"--dense_transfer: the file must hold an (h, w) integer tensor, got "
+                                 f"{tuple(labels.shape)} {labels.dtype}")
+        if tuple(labels.shape) != (S, S):
+            labels = torch.nn.functional.interpolate(labels[None, None].to(torch.float32), size=(S, S),
+                                                     mode="nearest")[0, 0]
+        labels = labels.to(torch.int64)
+        match = match_images(ldm, images[0], images, embedding,
+                             None if args.dense_tokens == "all" else indices.cpu(), device=args.device,
+                             layers=args.layers, noise_level=args.noise_level, augment_degrees=args.augment_degrees,
+                             augment_scale=args.augment_scale, augment_translate=args.augment_translate,
+                             augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                             upscale_size=S)
+        moved = transfer_labels(match, labels, max_cycle=args.dense_max_cycle, min_score=args.dense_min_score)
+        torch.save(match.index.cpu(), os.path.join(folder, "dense_index.pt"))
+        torch.save(match.score.cpu(), os.path.join(folder, "dense_score.pt"))
+        torch.save(match.cycle.cpu(), os.path.join(folder, "dense_cycle.pt"))
+        torch.save(moved.cpu(), os.path.join(folder, "dense_labels.pt"))
+        if have_masks:
+            masks = torch.stack([torch.as_tensor(it["mask"], dtype=torch.float32) for it in items])
+            iou = foreground_iou(moved, masks).cpu()
+            torch.save(iou, os.path.join(folder, "dense_fg_iou.pt"))
+            rest = iou[1:]
+            mean = float(rest.mean()) if rest.numel() else float("nan")
+            print(f"dense_transfer: mean foreground IoU {mean:.4f} over {rest.numel()} non-source images", flush=True)
+        if args.visualize:
+            m = min(12, M)
+            shown = images[:m].to(args.device, torch.float32)
+            label = torch.nn.functional.interpolate(moved[:m, None].float(), size=tuple(images.shape[-2:]),
+                                                    mode="nearest")[:, 0].long()
+            colors = ops.default_colors(int(moved.max().clamp_min(0)) + 1).to(args.device)
+            tint = (colors.float() / 255.0)[label.clamp_min(0)].permute(0, 3, 1, 2)
+            shown = torch.where((label >= 0)[:, None], 0.5 * shown + 0.5 * tint, shown)
+            _save_row_sheet(os.path.join(folder, "dense.png"), shown, match.token_points[:, :0], args.device)
+        print(f"dense_transfer: {M} images against the first at {S}, {match.token_points.shape[1]} tokens -> "
+              f"{os.path.join(folder, 'dense_labels.pt')}", flush=True)
+
+
 def predict_stage(args, ldm, controllers, batch=4):
     """``--start_from_stage predict``: the keypoints of every image of the dataset (built as
     ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
@@ -332,7 +416,7 @@ def predict_stage(args, ldm, controllers, batch=4):
     ``indices.pt``, and ``regressor.pt`` is not applied (it was fitted to other tokens).
     With ``--part_maps`` ``parts_stage`` first writes the part maps of the same images; the keypoints are
     the same bits with and without it.  With ``--transfer K`` ``transfer_stage`` does the same for the transferred
-    landmarks."""
+    landmarks, and with ``--dense_transfer SRC`` ``dense_stage`` for the dense field and the transferred labels."""
     from .datasets import make_dataset
     from .eval import predict_keypoints
     folder = args.save_folder
@@ -352,6 +436,8 @@ def predict_stage(args, ldm, controllers, batch=4):
         parts_stage(args, ldm, controllers, embedding, indices, dataset)
     if args.transfer is not None:
         transfer_stage(args, ldm, controllers, embedding, indices, dataset)
+    if args.dense_transfer is not None:
+        dense_stage(args, ldm, controllers, embedding, indices, dataset)
     names = _image_names(dataset)
     k = int(args.num_subjects)
     kps, regs, scos, refs, pks, vals = [], [], [], [], [], []
@@ -427,6 +513,10 @@ def main(argv=None):
         parser.error("--transfer must be at least 1 (the number of exemplar images)")
     if args.transfer_size < 2:
         parser.error("--transfer_size must be at least 2")
+    if args.dense_transfer is not None and args.start_from_stage != "predict":
+        parser.error("--dense_transfer belongs to --start_from_stage predict")
+    if args.dense_size < 2:
+        parser.error("--dense_size must be at least 2")
     from .launch import launcher_env, spawn_ranks
     # torch.cuda.device_count() does not initialise HIP on this image, so the ranks can still start
     n = ranks_to_start(args, torch.cuda.device_count(), launcher_env())

@@ -2360,3 +2360,63 @@ def tta_reduce_match(maps, theta_inv, queries, return_scores=False, return_avg=F
         return (_c(queries), Q), (B, n, 2), outs, nbytes, (Q,)
 
     return _tta_call("tta_reduce_match", maps, theta_inv, return_avg, query)
+
+
+# --------------------------------------------------------------------------- A19 dense match field
+def match_field_flops(B, n, P, Q):
+    """Flop model of skp_match_field: the (P, Q) products over n tokens of B images."""
+    return 2 * B * n * P * Q
+
+
+def match_field_bytes(B, n, P, Q, bx=None, by=None):
+    """Byte model of skp_match_field: what must cross the memory interface once — each distinct
+    operand read for its norms and once more for the products (``bx``, ``by`` operands: 1 where one
+    is shared, default B) and the index and score written.  The panels' re-reads by other workgroups
+    are cache traffic, and the (P, Q) product is never in memory."""
+    bx, by = B if bx is None else bx, B if by is None else by
+    return 2 * 4 * n * (bx * P + by * Q) + 8 * B * P
+
+
+def match_field(x, y):
+    """The dense nearest-pixel field (skp_match_field): for every column p of ``x`` the column q of
+    ``y`` with the greatest cosine, on the exact-f32 matrix cores; the (P, Q) product is never in memory.
+
+    ``x`` (B or 1, n, P) and ``y`` (B or 1, n, Q): float32, contiguous, on one device; a leading 1
+    beside a B is one operand shared by the B images.  A (B, n, S, S) TTA average is such an operand
+    as ``avg.view(B, n, S * S)``.  Returns ``(index (B, P) int32, score (B, P) float32)``: the lowest
+    usable q with the greatest key dot · (1 / |y_q|) and that key times 1 / |x_p|; −1 and −inf where
+    the column p is not usable (zero, or holding a NaN or an infinity) or no q is.  Norms and dots
+    are fmaf chains in token order (include/skp.h), so the result is defined bit for bit.
+    """
+    _lib.require_device(x, y)
+    for name, t in (("x", x), ("y", y)):
+        if t.dim() != 3:
+            raise ValueError(f"match_field: {name} must be (B or 1, n, pixels), got {tuple(t.shape)}")
+        if t.dtype != F32:
+            raise ValueError(f"match_field: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"match_field: {name} must be contiguous, got strides {t.stride()}")
+    if y.device != x.device:
+        raise ValueError(f"match_field: y on {y.device}, x on {x.device}")
+    (bx, n, P), (by, ny, Q) = x.shape, y.shape
+    if ny != n:
+        raise ValueError(f"match_field: y has {ny} tokens, x has {n}")
+    B = max(bx, by)
+    if bx not in (1, B):
+        raise ValueError(f"match_field: x has {bx} images, y has {by}")
+    if by not in (1, B):
+        raise ValueError(f"match_field: y has {by} images, x has {bx}")
+    dev = x.device
+    key = ("match_field", dev, B, n, P, Q)
+    ws = _TTA_WS.get(key)
+    if ws is None:
+        nbytes = _lib.lib().skp_match_field_workspace(B, n, P, Q)
+        if nbytes <= 0:
+            raise ValueError(f"match_field: bad shape B={B}, n={n}, P={P}, Q={Q}")
+        ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    index = torch.empty(B, P, device=dev, dtype=torch.int32)
+    score = torch.empty(B, P, device=dev, dtype=F32)
+    with _timed("skp_match_field", match_field_bytes(B, n, P, Q, bx, by), match_field_flops(B, n, P, Q)):
+        call("skp_match_field", ptr(x), n * P if bx == B and B > 1 else 0, P, ptr(y), n * Q if by == B and B > 1 else 0,
+             Q, B, n, ptr(index), ptr(score), ptr(ws), stream(dev))
+    return index, score
