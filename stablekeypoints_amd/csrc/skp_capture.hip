@@ -15,6 +15,7 @@
 // atomics), streams the row partials out, and a second kernel applies the vertical adjoint.
 #include <algorithm>
 
+#include "skp_capture.h"
 #include "skp_common.h"
 
 using namespace skp;
@@ -1117,8 +1118,9 @@ struct LayerPtrs {
 // registers, and transposes the (pixel, token) tile through LDS for token-major stores.
 constexpr int kAggP = 16;
 constexpr int kAggThreads = 256;
+constexpr int kAggSlabs = 2;   // slabs per iteration
 
-template <int NV, int SPI, bool NT>  // float4 loads/thread/slab; slabs per iteration; non-temporal loads
+template <int NV>  // float4 loads/thread/slab (non-temporal: a read-once stream)
 __global__ __launch_bounds__(kAggThreads) void aggregate_kernel(LayerPtrs lp, int L, int BH, int RR, int N,
                                                                 float count, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float tile[];   // kAggP*N floats
@@ -1130,30 +1132,26 @@ __global__ __launch_bounds__(kAggThreads) void aggregate_kernel(LayerPtrs lp, in
 #pragma unroll
   for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
   const int nslab = L * BH;
-  for (int sl = 0; sl < nslab; sl += SPI) {
-    float4 a[SPI][NV];
+  for (int sl = 0; sl < nslab; sl += kAggSlabs) {
+    float4 a[kAggSlabs][NV];
 #pragma unroll
-    for (int u = 0; u < SPI; ++u) {
+    for (int u = 0; u < kAggSlabs; ++u) {
       const int su = sl + u;
       const float* base = su < nslab ? lp.p[su / BH] + ((size_t)(su % BH) * RR + p0) * N : nullptr;
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         const int f = 4 * (t + v * kAggThreads);
         if (base && f < flat) {
-          if (NT) {
-            typedef float f4v __attribute__((ext_vector_type(4)));
-            const f4v w = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(base + f));
-            a[u][v] = make_float4(w.x, w.y, w.z, w.w);
-          } else {
-            a[u][v] = *reinterpret_cast<const float4*>(base + f);
-          }
+          typedef float f4v __attribute__((ext_vector_type(4)));
+          const f4v w = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(base + f));
+          a[u][v] = make_float4(w.x, w.y, w.z, w.w);
         } else {
           a[u][v] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
       }
     }
 #pragma unroll
-    for (int u = 0; u < SPI; ++u)
+    for (int u = 0; u < kAggSlabs; ++u)
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         acc[v].x += a[u][v].x; acc[v].y += a[u][v].y; acc[v].z += a[u][v].z; acc[v].w += a[u][v].w;
@@ -1241,11 +1239,27 @@ __global__ void bilinear_bwd_kernel(const float* __restrict__ gout, int C, int R
   gin[e] = acc;
 }
 
+// ------------------------------------------------------------------------------------ host side
+// Tokens per lane for N tokens: the width template argument of every capture kernel (-1: N > 1024)
+struct TokenWidth {
+  int fwd_nq;     // capture_fwd_kernel: float4 quads per lane, 256·NQ >= N
+  int bwd_nt;     // capture_bwd_rows_kernel: tokens per thread, 512·NT >= N
+  int maps_qpl;   // capture_maps_kernel: float4 quads per lane (16 lanes per pixel), 64·QPL >= N
+  int row_nq;     // capture_bwd_row_kernel: float4 quads per lane, 256·NQ >= N
+};
+TokenWidth token_width(int N) {
+  if (N <= 64) return {1, 1, 1, 1};
+  if (N <= 128) return {1, 1, 2, 1};
+  if (N <= 256) return {1, 1, 4, 1};
+  if (N <= 512) return {2, 1, 8, 2};
+  if (N <= 1024) return {4, 2, 16, 4};
+  return {-1, -1, -1, -1};
+}
+
 template <int NQ>
 void launch_fwd(const float* z, int BH, int s, int N, int R, float* attn, float2* stats, hipStream_t st) {
   const size_t lds = (size_t)s * NQ * 4 * WAVE * sizeof(float);
-  const bool vec = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(z) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(attn) & 15) == 0);
+  const bool vec = N % 4 == 0 && aligned16(z) && aligned16(attn);
   // Non-temporal stores measured faster at s = 32 (64 KiB LDS, 2 blocks/CU: 96 -> 75-84 us) and
   // slower at s = 16 (5 blocks/CU: 55 -> 80 us), N = 500, R = 128 (tools/kbench.py).
   const bool nts = lds > 48 * 1024;
@@ -1258,7 +1272,10 @@ void launch_fwd(const float* z, int BH, int s, int N, int R, float* attn, float2
     hipLaunchKernelGGL((capture_fwd_kernel<NQ, false>), dim3(BH * R), dim3(kThreads), lds, st, z, BH, s, N, R, attn, stats);
 }
 
-size_t bwd_rows_lds(int s, int N, int R, int CH);
+size_t bwd_rows_lds(int s, int N, int R, int CH) {
+  const size_t np = (size_t)token_width(N).bwd_nt * kBwdThreads;
+  return (s * np + (size_t)CH * (np + 4) + (size_t)R * 4 + (((size_t)R + 3) & ~(size_t)3)) * sizeof(float);
+}
 
 template <int NT>
 void launch_bwd_rows(const float* z, int BH, int s, int N, int R, int CH, const float* g, int group, long long sb,
@@ -1267,25 +1284,6 @@ void launch_bwd_rows(const float* z, int BH, int s, int N, int R, int CH, const 
   const int share = sb == 0 ? BH : group;   // heads reading the same gradient rows
   hipLaunchKernelGGL((capture_bwd_rows_kernel<NT>), dim3(BH * R), dim3(kBwdThreads), lds, st, z, BH, s, N, R, CH, g,
                      group, sb, sp, sn, gscale, share, stats, ws);
-}
-
-int nt_for(int N);
-size_t bwd_rows_lds(int s, int N, int R, int CH) {
-  const size_t np = (size_t)nt_for(N) * kBwdThreads;
-  return (s * np + (size_t)CH * (np + 4) + (size_t)R * 4 + (((size_t)R + 3) & ~(size_t)3)) * sizeof(float);
-}
-
-int nq_for(int N) {  // float4 quads per lane for the forward
-  if (N <= 256) return 1;
-  if (N <= 512) return 2;
-  if (N <= 1024) return 4;
-  return -1;
-}
-
-int nt_for(int N) {  // tokens per thread for the backward
-  if (N <= 512) return 1;
-  if (N <= 1024) return 2;
-  return -1;
 }
 
 // chunk of output pixels for the backward: the largest multiple of 4 dividing R (enables the
@@ -1307,7 +1305,7 @@ extern "C" int skp_capture_fwd(const float* z_low, int BH, int s, int N, int R, 
                                void* stream) {
   SKP_CHECK_ARG(z_low && attn, "null pointer");
   SKP_CHECK_ARG(BH > 0 && s > 0 && R > 0 && N > 0, "non-positive shape");
-  const int nq = nq_for(N);
+  const int nq = token_width(N).fwd_nq;
   SKP_CHECK_ARG(nq > 0, "N > 1024 tokens is not supported");
   SKP_CHECK_ARG((size_t)s * nq * 4 * WAVE * 4 <= 160 * 1024, "s*N too large for LDS");
   hipStream_t st = as_stream(stream);
@@ -1328,7 +1326,7 @@ extern "C" int skp_capture_bwd(const float* z_low, int BH, int s, int N, int R, 
   SKP_CHECK_ARG(BH > 0 && s > 0 && R > 0 && N > 0, "non-positive shape");
   SKP_CHECK_ARG(R <= 1024, "R > 1024 is not supported");
   SKP_CHECK_ARG(BH <= 65535, "BH > 65535");
-  const int nt = nt_for(N);
+  const int nt = token_width(N).bwd_nt;
   SKP_CHECK_ARG(nt > 0, "N > 1024 tokens is not supported");
   const int CH = pick_chunk(s, N, R);
   SKP_CHECK_ARG(bwd_rows_lds(s, N, R, CH) <= 160 * 1024, "s*N too large for LDS");
@@ -1345,15 +1343,6 @@ extern "C" int skp_capture_bwd(const float* z_low, int BH, int s, int N, int R, 
 }
 
 namespace {
-int maps_qpl(int N) {   // float4 quads per lane (16 lanes per pixel): Np = 64·QPL >= N
-  if (N <= 64) return 1;
-  if (N <= 128) return 2;
-  if (N <= 256) return 4;
-  if (N <= 512) return 8;
-  if (N <= 1024) return 16;
-  return -1;
-}
-
 // floats per V buffer: the widest layer's nc × Np, and at least half the store tile (P × 132)
 int maps_vstride(const int* sizes, int L, int R, int qpl, int waves) {
   const int P = waves * maps_pxw(qpl);
@@ -1398,28 +1387,24 @@ void launch_maps(const CapLayers& cl, int L, int B, int H, int N, int R, int vst
 
 extern "C" int skp_capture_maps_fwd(const float* const* z_low, const int* sizes, int L, int B, int H, int N, int R,
                                     float* maps, float* const* stats, void* stream) {
-  SKP_CHECK_ARG(z_low && sizes && maps, "null pointer");
-  SKP_CHECK_ARG(L > 0 && L <= SKP_MAX_LAYERS, "L out of range");
-  SKP_CHECK_ARG(B > 0 && H > 0 && N > 0 && R > 0, "non-positive shape");
+  const char* err = maps_shape_error(z_low && sizes && maps, L, B, H, N, R);
+  SKP_CHECK_ARG(!err, err);
   SKP_CHECK_ARG((long long)B * R * R <= (1LL << 31) && (long long)B * H <= 65535, "shape too large");
-  const int qpl = maps_qpl(N);
+  const int qpl = token_width(N).maps_qpl;
   SKP_CHECK_ARG(qpl > 0, "N > 1024 tokens is not supported");
+  err = maps_layers_error(z_low, nullptr, nullptr, sizes, L, N, R, false, true);
+  SKP_CHECK_ARG(!err, err);
+  const int vstride = maps_vstride(sizes, L, R, qpl, kMapWaves);
+  const size_t lds = maps_lds(vstride, qpl, kMapWaves);
+  SKP_CHECK_ARG(lds <= 160 * 1024, "s*N too large for LDS");
   CapLayers cl{};
-  bool aligned = (N % 4) == 0;
   for (int l = 0; l < L; ++l) {
-    SKP_CHECK_ARG(z_low[l], "null layer pointer");
-    SKP_CHECK_ARG(sizes[l] > 0 && sizes[l] <= R, "layer size must be in [1, R]");
     cl.z[l] = z_low[l];
     cl.s[l] = sizes[l];
     cl.sc[l] = (float)sizes[l] / (float)R;
     cl.stats[l] = stats ? reinterpret_cast<float2*>(stats[l]) : nullptr;
-    aligned = aligned && ((reinterpret_cast<uintptr_t>(z_low[l]) & 15) == 0);
   }
-  SKP_CHECK_ARG(aligned || (N % 4) != 0, "z_low pointers must be 16-B aligned");
   hipStream_t st = as_stream(stream);
-  const int vstride = maps_vstride(sizes, L, R, qpl, kMapWaves);
-  const size_t lds = maps_lds(vstride, qpl, kMapWaves);
-  SKP_CHECK_ARG(lds <= 160 * 1024, "s*N too large for LDS");
   switch (qpl) {
     case 1: launch_maps<1>(cl, L, B, H, N, R, vstride, lds, maps, st); break;
     case 2: launch_maps<2>(cl, L, B, H, N, R, vstride, lds, maps, st); break;
@@ -1452,26 +1437,21 @@ void launch_bwd_row(const float* z, int B, int H, int s, int N, int R, const flo
 extern "C" int skp_capture_maps_bwd(const float* const* z_low, const int* sizes, int L, int B, int H, int N, int R,
                                     const float* dmaps, float gscale, const float* const* stats, float* const* dz_low,
                                     float* workspace, void* stream) {
-  SKP_CHECK_ARG(z_low && sizes && dmaps && dz_low && workspace, "null pointer");
-  SKP_CHECK_ARG(L > 0 && L <= SKP_MAX_LAYERS, "L out of range");
-  SKP_CHECK_ARG(B > 0 && H > 0 && N > 0 && R > 0, "non-positive shape");
+  const char* err = maps_shape_error(z_low && sizes && dmaps && dz_low && workspace, L, B, H, N, R);
+  SKP_CHECK_ARG(!err, err);
   SKP_CHECK_ARG(N % 4 == 0, "N must be a multiple of 4 (use skp_capture_bwd)");
   SKP_CHECK_ARG(N <= 1024, "N > 1024 tokens is not supported");
   SKP_CHECK_ARG(R <= 1024, "R > 1024 is not supported (capture_bwd_cols_kernel tap tables)");
-  SKP_CHECK_ARG(bwd_row_lds(R, N <= 256 ? 1 : (N <= 512 ? 2 : 4)) <= 160 * 1024, "R * N too large for LDS");
+  const int nq = token_width(N).row_nq;
+  SKP_CHECK_ARG(bwd_row_lds(R, nq) <= 160 * 1024, "R * N too large for LDS");
   SKP_CHECK_ARG((long long)B * H <= 65535 && (long long)B * H * R < (1LL << 31), "shape too large");
-  SKP_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "workspace must be 16-B aligned");
-  int smax = 0;
-  for (int l = 0; l < L; ++l) {
-    SKP_CHECK_ARG(z_low[l] && dz_low[l], "null layer pointer");
-    SKP_CHECK_ARG(sizes[l] > 0 && sizes[l] <= R && sizes[l] <= 1024, "layer size must be in [1, R]");
-    SKP_CHECK_ARG((reinterpret_cast<uintptr_t>(z_low[l]) & 15) == 0, "z_low pointers must be 16-B aligned");
-    smax = std::max(smax, sizes[l]);
-  }
+  SKP_CHECK_ARG(aligned16(workspace), "workspace must be 16-B aligned");
+  err = maps_layers_error(z_low, nullptr, dz_low, sizes, L, N, R, false, false);
+  SKP_CHECK_ARG(!err, err);
   hipStream_t st = as_stream(stream);
   const int P = R * R;
-  float* gT = workspace;                                   // (B, R², N)
-  float* ws = workspace + (size_t)B * P * N;               // (B·H, R, s, N) row partials, reused per layer
+  float* gT = workspace;
+  float* ws = workspace + maps_bwd_ws(sizes, L, B, H, N, R).rows;
   if ((P % 4) == 0 && (reinterpret_cast<uintptr_t>(dmaps) & 15) == 0)   // N % 4 == 0 is checked above
     hipLaunchKernelGGL(transpose_scale4_kernel, dim3((P + 63) / 64, (N + 63) / 64, B), dim3(256), 0, st, dmaps, N, P,
                        gscale, gT);
@@ -1479,13 +1459,12 @@ extern "C" int skp_capture_maps_bwd(const float* const* z_low, const int* sizes,
     hipLaunchKernelGGL(transpose_scale_kernel, dim3((P + 63) / 64, (N + 63) / 64, B), dim3(256), 0, st, dmaps, N, P,
                        gscale, gT);
   SKP_LAUNCH_CHECK();
-  const int nq = N / 4;
   for (int l = 0; l < L; ++l) {
     const int s = sizes[l];
     // the row kernel reads the stats as float4 pixel pairs: 16-B aligned rows need an even R
     const float* stl = (stats && (R % 2) == 0) ? stats[l] : nullptr;
-    if (nq <= 64) launch_bwd_row<1>(z_low[l], B, H, s, N, R, gT, stl, ws, st);
-    else if (nq <= 128) launch_bwd_row<2>(z_low[l], B, H, s, N, R, gT, stl, ws, st);
+    if (nq == 1) launch_bwd_row<1>(z_low[l], B, H, s, N, R, gT, stl, ws, st);
+    else if (nq == 2) launch_bwd_row<2>(z_low[l], B, H, s, N, R, gT, stl, ws, st);
     else launch_bwd_row<4>(z_low[l], B, H, s, N, R, gT, stl, ws, st);
     SKP_LAUNCH_CHECK();
     // (a float4 form of this kernel measured the same 81 µs: it streams the row partials at
@@ -1495,7 +1474,6 @@ extern "C" int skp_capture_maps_bwd(const float* const* z_low, const int* sizes,
                        dz_low[l]);
     SKP_LAUNCH_CHECK();
   }
-  (void)smax;
   return SKP_OK;
 }
 
@@ -1529,7 +1507,7 @@ extern "C" int skp_aggregate(const float* const* layers, int L, int BH, int RR, 
       // 2 slabs per iteration, non-temporal 16-B loads (read-once stream: +11% over cached loads,
       // 6.0 vs 5.35 TB/s on N=500 / R=128 / 4 layers × 8 heads, tools/kbench.py)
 #define SKP_AGG(NV) \
-  hipLaunchKernelGGL((aggregate_kernel<NV, 2, true>), grid, dim3(kAggThreads), lds, st, lp, L, BH, RR, N, count, out)
+  hipLaunchKernelGGL((aggregate_kernel<NV>), grid, dim3(kAggThreads), lds, st, lp, L, BH, RR, N, count, out)
       if (nv <= 1) SKP_AGG(1);
       else if (nv <= 2) SKP_AGG(2);
       else if (nv <= 4) SKP_AGG(4);

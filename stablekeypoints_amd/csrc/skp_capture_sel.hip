@@ -39,6 +39,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "skp_capture.h"
 #include "skp_common.h"
 
 using namespace skp;
@@ -81,19 +82,12 @@ __global__ void sel_gather_kernel(SelSmall t, int L, int BH, int N, int H, const
   zsel[e] = (tk >= 0 && tk < N) ? t.z[l][bq * N + tk] : 0.0f;
 }
 
-// The per-pixel pair sel_dense reads: (mb, d) with d = −dot and a = exp2(z·log2e + mb).  With
-// SKP_SEL_DFOLD (default) |d| is folded into the exponent, (mb + log2|d|, d): sel_dense then gets
-// a·|d| from its exp2 and d's sign from its tap weights' sign bits (scalar xors), one packed
-// multiply per (pixel, token pair) less (d = 0 gives exp2(−inf) = 0).
-#ifndef SKP_SEL_DFOLD
-#define SKP_SEL_DFOLD 1
-#endif
+// The per-pixel pair sel_dense reads: (mb, d) with d = −dot and a = exp2(z·log2e + mb).  |d| is
+// folded into the exponent, (mb + log2|d|, d): sel_dense then gets a·|d| from its exp2 and d's
+// sign from its tap weights' sign bits (scalar xors), one packed multiply per (pixel, token pair)
+// less than with (mb, d) (d = 0 gives exp2(−inf) = 0).
 __device__ __forceinline__ float2 sel_pix(float mb, float dot) {
-#if SKP_SEL_DFOLD
   return make_float2(mb + __builtin_amdgcn_logf(fabsf(dot)), -dot);   // v_log_f32 = log2
-#else
-  return make_float2(mb, -dot);
-#endif
 }
 
 // output indices whose taps can reach low-res index j: src ∈ [j − 2, j + 2) (clamped edges included)
@@ -485,7 +479,7 @@ __device__ __forceinline__ void sel_dense_body(const SelLayers& sl, int BH, int 
         const int c0 = lo_rel(t, RATIO) + 2;                             // band slot of the first tap
         // (mb, d), uniform per band: a scalar load where the band is the wave (read-only here)
         float2 pd;
-        if constexpr (LW == WAVE && SKP_SEL_DFOLD) {
+        if constexpr (LW == WAVE) {
           using cu64 = __attribute__((address_space(4))) const unsigned long long;
           pd = __builtin_bit_cast(float2, reinterpret_cast<cu64*>(reinterpret_cast<uintptr_t>(pp))[t]);
         } else {
@@ -499,19 +493,15 @@ __device__ __forceinline__ void sel_dense_body(const SelLayers& sl, int BH, int 
         ex.x = __builtin_amdgcn_exp2f(ex.x);
         ex.y = __builtin_amdgcn_exp2f(ex.y);
         float w4[4] = {wt[ut][0], wt[ut][1], wt[ut][2], wt[ut][3]};
-#if SKP_SEL_DFOLD
         if constexpr (LW == WAVE) {
           // ex = a·|d| (sel_pix); d's sign (uniform: one band per wave) flips the tap weights'
           // sign bits in SGPRs — no VALU
           const unsigned sg = __builtin_bit_cast(unsigned, pd.y) & 0x80000000u;
 #pragma unroll
           for (int m = 0; m < 4; ++m) w4[m] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, w4[m]) ^ sg);
-        } else {   // two bands per wave: the sign as a packed multiply, as without the fold
+        } else {   // two bands per wave: the sign as a packed multiply
           ex *= (f2)__builtin_copysignf(1.0f, pd.y);
         }
-#else
-        ex *= pd.y;
-#endif
         Hs[c0] = __builtin_elementwise_fma(ex, (f2)w4[0], Hs[c0]);
         Hs[c0 + 1] = __builtin_elementwise_fma(ex, (f2)w4[1], Hs[c0 + 1]);
         Hs[c0 + 2] = __builtin_elementwise_fma(ex, (f2)w4[2], Hs[c0 + 2]);
@@ -607,51 +597,34 @@ void launch_dense_pair(const SelLayers& sa, int na, const SelLayers& sb, int nb,
                      st, sa, nca, ja, sb, ncb, jb, BH, H, N, K, tok);
 }
 
-#ifndef SKP_SEL_PAIR
-#define SKP_SEL_PAIR 1   // 0: one sel_dense launch per layer size (A/B build)
-#endif
+// the (R, S) pairs with a compiled sel_dense kernel
+#define SKP_SEL_PAIRS(X) X(128, 16) X(128, 32) X(128, 8) X(64, 16) X(64, 8) X(64, 4) X(32, 8) X(32, 4)
 
-// (R, S) pairs with a compiled sel_dense kernel
 bool dense_launch(int R, int S, const SelLayers& sl, int nl, int BH, int H, int N, int K, const long long* tok,
                   hipStream_t st) {
-#define SKP_SEL_CASE(RR, SS)                                               \
-  if (R == RR && S == SS) {                                               \
-    launch_dense<RR / SS, SS>(sl, nl, BH, H, N, K, tok, st);               \
-    return true;                                                          \
+#define SKP_SEL_CASE(RR, SS)                                 \
+  if (R == RR && S == SS) {                                 \
+    launch_dense<RR / SS, SS>(sl, nl, BH, H, N, K, tok, st); \
+    return true;                                            \
   }
-  SKP_SEL_CASE(128, 16)
-  SKP_SEL_CASE(128, 32)
-  SKP_SEL_CASE(128, 8)
-  SKP_SEL_CASE(64, 16)
-  SKP_SEL_CASE(64, 8)
-  SKP_SEL_CASE(64, 4)
-  SKP_SEL_CASE(32, 8)
-  SKP_SEL_CASE(32, 4)
+  SKP_SEL_PAIRS(SKP_SEL_CASE)
 #undef SKP_SEL_CASE
   return false;
+}
+
+bool dense_supported(int R, int S) {
+#define SKP_SEL_CASE(RR, SS) || (R == RR && S == SS)
+  return false SKP_SEL_PAIRS(SKP_SEL_CASE);
+#undef SKP_SEL_CASE
 }
 
 // the SD-1.5 capture layers at R = 128 (s = 16 ×3 and s = 32) as one sel_dense_pair launch
 bool dense_pair_launch(int R, int SA, const SelLayers& sa, int na, int SB, const SelLayers& sb, int nb, int BH, int H,
                        int N, int K, const long long* tok, hipStream_t st) {
-#if SKP_SEL_PAIR
-  if (R == 128 && SA == 16 && SB == 32) {
-    launch_dense_pair<128, 16, 128, 32>(sa, na, sb, nb, BH, H, N, K, tok, st);
-    return true;
-  }
-  if (R == 128 && SA == 32 && SB == 16) {
-    launch_dense_pair<128, 16, 128, 32>(sb, nb, sa, na, BH, H, N, K, tok, st);
-    return true;
-  }
-#endif
-  return false;
-}
-
-bool dense_supported(int R, int S) {
-  const int pairs[][2] = {{128, 16}, {128, 32}, {128, 8}, {64, 16}, {64, 8}, {64, 4}, {32, 8}, {32, 4}};
-  for (auto& p : pairs)
-    if (p[0] == R && p[1] == S) return true;
-  return false;
+  if (R != 128 || std::min(SA, SB) != 16 || std::max(SA, SB) != 32) return false;
+  if (SA == 16) launch_dense_pair<128, 16, 128, 32>(sa, na, sb, nb, BH, H, N, K, tok, st);
+  else launch_dense_pair<128, 16, 128, 32>(sb, nb, sa, na, BH, H, N, K, tok, st);
+  return true;
 }
 
 // dense gradient from the sparse one (fallback): g[b][tok_k][p] = Σ_k gsel[b][k][p] (k order)
@@ -677,25 +650,6 @@ void launch_doth(const SelSmall& t, int L, int BH, int R, int H, int K, int smax
   else
     hipLaunchKernelGGL((sel_doth_kernel<RMAX, SEL_MAXK>), dim3((unsigned)(L * BH * R)), dim3(R), lds, st, t, zsel, BH, R,
                        H, K, tok, gsel, gscale, smax, hs, pix);
-}
-
-struct SelWs {   // workspace carve-up (floats)
-  size_t zsel, hs, pix, es, total;
-};
-SelWs sel_ws(const int* sizes, int L, int B, int H, int R, int K) {
-  SelWs w{};
-  size_t smax = 1;
-  for (int l = 0; l < L; ++l) smax = std::max(smax, (size_t)sizes[l]);
-  const size_t smax2 = smax * smax;
-  const size_t BH = (size_t)B * H, RR = (size_t)R * R;
-  size_t zs = 0;
-  for (int l = 0; l < L; ++l) zs += BH * (size_t)sizes[l] * sizes[l] * K;
-  w.zsel = 0;
-  w.hs = w.zsel + ((zs + 3) & ~(size_t)3);                // sel_doth's Hs rows [l][bh][k][R][smax]
-  w.pix = w.hs + (((size_t)L * BH * K * R * smax + 3) & ~(size_t)3);
-  w.es = w.pix + (size_t)L * BH * RR * 2;
-  w.total = w.es + (size_t)L * BH * K * smax2;
-  return w;
 }
 
 // Per-phase timing of the fast path (skp_sel_bwd_timing*): when enabled, each call records 5 events
@@ -737,59 +691,70 @@ bool fast_path(const int* sizes, int L, int R, int N) {
   return true;
 }
 
+// workspace carve-up (floats).  fast: zsel at 0, sel_doth's Hs rows, the (mb, d) pairs, es;
+// fallback: the dense (B, N, R²) gradient at 0, then skp_capture_maps_bwd's workspace
+struct SelWs {
+  bool fast;
+  size_t hs, pix, es, bwd, total;
+};
+SelWs sel_ws(const int* sizes, int L, int B, int H, int N, int R, int K) {
+  SelWs w{fast_path(sizes, L, R, N)};
+  const size_t smax = widest_layer(sizes, L);
+  const size_t BH = (size_t)B * H, RR = (size_t)R * R;
+  if (w.fast) {
+    size_t zs = 0;
+    for (int l = 0; l < L; ++l) zs += BH * (size_t)sizes[l] * sizes[l] * K;
+    w.hs = (zs + 3) & ~(size_t)3;                           // sel_doth's Hs rows [l][bh][k][R][smax]
+    w.pix = w.hs + (((size_t)L * BH * K * R * smax + 3) & ~(size_t)3);
+    w.es = w.pix + (size_t)L * BH * RR * 2;
+    w.total = w.es + (size_t)L * BH * K * smax * smax;
+  } else {
+    w.bwd = ((size_t)B * N * RR + 3) & ~(size_t)3;
+    w.total = (size_t)B * N * RR + maps_bwd_ws(sizes, L, B, H, N, R).total + 4;   // 4: the rounding of bwd
+  }
+  return w;
+}
+
 }  // namespace
 
 extern "C" long long skp_capture_maps_bwd_sel_workspace(const int* sizes, int L, int B, int H, int N, int R, int K) {
-  if (!sizes || L <= 0 || L > SKP_MAX_LAYERS || B <= 0 || H <= 0 || N <= 0 || R <= 0 || K <= 0) return -1;
-  int smax = 1;
-  for (int l = 0; l < L; ++l) smax = std::max(smax, sizes[l]);
-  if (fast_path(sizes, L, R, N)) return (long long)sel_ws(sizes, L, B, H, R, K).total;
-  // fallback: the dense (B, N, R²) gradient + skp_capture_maps_bwd's workspace
-  const long long RR = (long long)R * R;
-  return (long long)B * N * RR + (long long)B * RR * N + (long long)B * H * R * smax * N + 4;
+  if (maps_shape_error(sizes != nullptr, L, B, H, N, R) || K <= 0) return -1;
+  return (long long)sel_ws(sizes, L, B, H, N, R, K).total;
 }
 
 extern "C" int skp_capture_maps_bwd_sel(const float* const* z_low, const int* sizes, int L, int B, int H, int N, int R,
                                         const long long* sel_tok, int K, const float* gsel, float gscale,
                                         const float* const* stats, float* const* dz_low, float* workspace,
                                         void* stream) {
-  SKP_CHECK_ARG(z_low && sizes && sel_tok && gsel && stats && dz_low && workspace, "null pointer");
-  SKP_CHECK_ARG(L > 0 && L <= SKP_MAX_LAYERS, "L out of range");
-  SKP_CHECK_ARG(B > 0 && H > 0 && N > 0 && R > 0, "non-positive shape");
+  const char* err = maps_shape_error(z_low && sizes && sel_tok && gsel && stats && dz_low && workspace, L, B, H, N, R);
+  SKP_CHECK_ARG(!err, err);
   SKP_CHECK_ARG(R % 4 == 0, "R must be a multiple of 4");
   SKP_CHECK_ARG(K > 0 && K <= SEL_MAXK, "K must be in [1, 32]");
   SKP_CHECK_ARG(N % 4 == 0 && N <= 1024, "N must be a multiple of 4, at most 1024");
   SKP_CHECK_ARG((long long)B * H <= 65535 && (long long)B * H * R * R < (1LL << 31), "shape too large");
-  SKP_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "workspace must be 16-B aligned");
-  for (int l = 0; l < L; ++l) {
-    SKP_CHECK_ARG(z_low[l] && dz_low[l] && stats[l], "null layer pointer");
-    SKP_CHECK_ARG(sizes[l] > 0 && sizes[l] <= R, "layer size must be in [1, R]");
-    SKP_CHECK_ARG((reinterpret_cast<uintptr_t>(z_low[l]) & 15) == 0 && (reinterpret_cast<uintptr_t>(dz_low[l]) & 15) == 0,
-                  "z_low / dz_low pointers must be 16-B aligned");
-  }
+  SKP_CHECK_ARG(aligned16(workspace), "workspace must be 16-B aligned");
+  err = maps_layers_error(z_low, stats, dz_low, sizes, L, N, R, true, false);
+  SKP_CHECK_ARG(!err, err);
   hipStream_t st = as_stream(stream);
   const int BH = B * H;
   const size_t RR = (size_t)R * R;
-  if (!fast_path(sizes, L, R, N)) {
+  const SelWs wsz = sel_ws(sizes, L, B, H, N, R, K);
+  if (!wsz.fast) {
     // no compiled kernel for this (R, s): scatter into a dense gradient, then the dense backward
     float* g = workspace;
     SKP_CHECK_ARG(hipMemsetAsync(g, 0, (size_t)B * N * RR * sizeof(float), st) == hipSuccess, "memset failed");
     hipLaunchKernelGGL(sel_scatter_kernel, dim3((unsigned)(((size_t)B * RR + 255) / 256)), dim3(256), 0, st, sel_tok,
                        gsel, B, K, N, (long long)RR, g);
     SKP_LAUNCH_CHECK();
-    float* rest = workspace + (((size_t)B * N * RR + 3) & ~(size_t)3);
-    return skp_capture_maps_bwd(z_low, sizes, L, B, H, N, R, g, gscale, stats, dz_low, rest, stream);
+    return skp_capture_maps_bwd(z_low, sizes, L, B, H, N, R, g, gscale, stats, dz_low, workspace + wsz.bwd, stream);
   }
-  const SelWs wsz = sel_ws(sizes, L, B, H, R, K);
-  float* zsel = workspace + wsz.zsel;
+  float* zsel = workspace;
   float* hs = workspace + wsz.hs;
   float2* pix = reinterpret_cast<float2*>(workspace + wsz.pix);
   float* es = workspace + wsz.es;
-  int smax = 1, rmax = 1;
-  for (int l = 0; l < L; ++l) {
-    smax = std::max(smax, sizes[l]);
-    rmax = std::max(rmax, R / sizes[l]);
-  }
+  const int smax = widest_layer(sizes, L);
+  int rmax = 1;
+  for (int l = 0; l < L; ++l) rmax = std::max(rmax, R / sizes[l]);
   SelSmall t{};
   t.zoff[0] = 0;
   for (int l = 0; l < L; ++l) {

@@ -203,17 +203,35 @@ def capture_logits(q, k, scale):
 
 
 # --------------------------------------------------------------------------- A1 capture
+def _layer_ptrs(tensors, offset=0):
+    """The C ABI's array of per-layer device pointers (void* const*), each ``offset`` bytes in."""
+    arr = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() + offset for t in tensors])
+    return ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
+
+
+def _layer_sizes(sizes):
+    """The C ABI's array of per-layer sizes (const int*)."""
+    return (ctypes.c_int * len(sizes))(*[int(s) for s in sizes])
+
+
+def _capture_fwd_run(z, s, R, with_stats=False):
+    """skp_capture_fwd: (attn (BH, R², N), the per-pixel softmax (max, 1/Σ) (BH, R², 2) or None)."""
+    BH, S, N = z.shape
+    assert S == s * s
+    attn = torch.empty(BH, R * R, N, device=z.device, dtype=F32)
+    stats = torch.empty(BH, R * R, 2, device=z.device, dtype=F32) if with_stats else None
+    with _timed("skp_capture_fwd", (BH * R * R * N + BH * S * N) * 4):
+        call("skp_capture_fwd", ptr(z), BH, s, N, R, ptr(attn), ptr(stats), stream(z.device))
+    return attn, stats
+
+
 class CaptureAttn(torch.autograd.Function):
     """attn = softmax_N(bicubic_{s→R}(z_low)) — the captured map (ptp_utils.py:513-536)."""
 
     @staticmethod
     def forward(ctx, z, s, R):
         z = _c(z)
-        BH, S, N = z.shape
-        assert S == s * s
-        attn = torch.empty(BH, R * R, N, device=z.device, dtype=F32)
-        with _timed("skp_capture_fwd", (BH * R * R * N + BH * S * N) * 4):
-            call("skp_capture_fwd", ptr(z), BH, s, N, R, ptr(attn), None, stream(z.device))
+        attn, _ = _capture_fwd_run(z, s, R)
         ctx.save_for_backward(z)
         ctx.s, ctx.R = s, R
         return attn
@@ -237,11 +255,11 @@ def capture_bwd(z, s, R, dattn, gscale=1.0, group=1, strides=None, stats=None):
             sb = 0
     else:
         sb, sp, sn = strides
-    ws = torch.empty(BH, R, s, N, device=z.device, dtype=F32)
+    ws = torch.empty(capture_bwd_ws_floats(BH, s, N, R), device=z.device, dtype=F32)
     dz = torch.empty_like(z)
     with _timed("skp_capture_bwd", (BH * S * N * 2 + BH * R * s * N * 2) * 4):
         call("skp_capture_bwd", ptr(z), BH, s, N, R, ptr(dattn), int(group), sb, sp, sn, float(gscale),
-             ptr(stats) if stats is not None else None, ptr(dz), ptr(ws), stream(z.device))
+             ptr(stats), ptr(dz), ptr(ws), stream(z.device))
     return dz
 
 
@@ -260,13 +278,12 @@ class _Aggregate(torch.autograd.Function):
             if t.shape != layers[0].shape:
                 raise ValueError("collect_maps: captured layers must share (BH, R*R, N); got "
                                  f"{[tuple(x.shape) for x in layers]}")
-        arr = (ctypes.c_void_p * len(layers))(*[t.data_ptr() for t in layers])
         n_out = N if indices is None else int(indices.numel())
         out = torch.empty(n_out, R, R, device=layers[0].device, dtype=F32)
         idx = None if indices is None else indices.to(device=out.device, dtype=torch.int64).contiguous()
         with _timed("skp_aggregate", (len(layers) * BH * RR * N + n_out * RR) * 4):
-            call("skp_aggregate", ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)), len(layers), BH, RR, N,
-                 ptr(idx), n_out, ptr(out), stream(out.device))
+            call("skp_aggregate", _layer_ptrs(layers), len(layers), BH, RR, N, ptr(idx), n_out, ptr(out),
+                 stream(out.device))
         ctx.meta = (BH, RR, N, R, len(layers))
         ctx.idx = idx
         ctx.upsample_res = upsample_res
@@ -357,6 +374,16 @@ def capture_maps_bwd_bytes(B, H, N, R, sizes):
     return 4 * (3 * B * N * RR + sum(2 * B * H * s * s * N + 2 * B * H * RR + 2 * B * H * R * s * N for s in sizes))
 
 
+def capture_bwd_ws_floats(BH, s, N, R):
+    """Floats of skp_capture_bwd's workspace: the (BH, R, s, N) row partials."""
+    return BH * R * s * N
+
+
+def capture_maps_bwd_ws_floats(B, H, N, R, sizes):
+    """Floats of skp_capture_maps_bwd's workspace: the (B, R², N) gradient, then the widest row partials."""
+    return B * R * R * N + capture_bwd_ws_floats(B * H, max(sizes), N, R)
+
+
 class CaptureMaps(torch.autograd.Function):
     """Per-image maps straight from the captured layers' logits (fused capture + aggregate).
 
@@ -372,27 +399,18 @@ class CaptureMaps(torch.autograd.Function):
     def forward(ctx, B, R, sizes, *zs):
         zs = [_c16(z) for z in zs]
         BH, _, N = zs[0].shape
-        H = BH // B
-        L = len(zs)
-        dev = zs[0].device
-        RR = R * R
+        H, L = BH // B, len(zs)
+        dev, RR = zs[0].device, R * R
         if FUSED_MAPS:
             out, stats = _capture_maps_run(zs, sizes, B, R)
         else:
-            # per-pixel softmax (max, 1/Σ) of every layer, kept for the backward (8 B per pixel-head)
-            stats = [torch.empty(BH, RR, 2, device=dev, dtype=F32) for _ in range(L)]
+            # every layer's attention and softmax stats (kept for the backward), then each image's map
+            attn, stats = zip(*[_capture_fwd_run(z, s, R, with_stats=True) for z, s in zip(zs, sizes)])
             out = torch.empty(B, N, R, R, device=dev, dtype=F32)
-            attn = [torch.empty(BH, RR, N, device=dev, dtype=F32) for _ in range(L)]
-            for z, a, st, s in zip(zs, attn, stats, sizes):
-                with _timed("skp_capture_fwd", (BH * RR * N + BH * s * s * N) * 4):
-                    call("skp_capture_fwd", ptr(z), BH, s, N, R, ptr(a), ptr(st), stream(dev))
             for b in range(B):
-                off = b * H * RR * N * 4
-                arr = (ctypes.c_void_p * L)(*[a.data_ptr() + off for a in attn])
                 with _timed("skp_aggregate", (L * H * RR * N + N * RR) * 4):
-                    call("skp_aggregate", ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)), L, H, RR, N, None, N,
-                         ptr(out[b]), stream(dev))
-            del attn
+                    call("skp_aggregate", _layer_ptrs(attn, b * H * RR * N * 4), L, H, RR, N, None, N, ptr(out[b]),
+                         stream(dev))
         ctx.save_for_backward(*zs, *stats)
         ctx.meta = (B, H, R, N, list(sizes))
         return out
@@ -408,22 +426,15 @@ class CaptureMaps(torch.autograd.Function):
         """dz_low of every layer for a dense per-image map gradient dmaps (B, N, R, R)."""
         B, H, R, N, sizes = meta
         dmaps = _c(dmaps)                       # (B, N, R, R)
-        RR = R * R
-        scale = 1.0 / float(len(zs) * H)
-        L = len(zs)
+        RR, L = R * R, len(zs)
+        scale = 1.0 / float(L * H)
         if FUSED_MAPS and N % 4 == 0:
             dzs = [torch.empty_like(z) for z in zs]
-            ws = torch.empty(B * RR * N + B * H * R * max(sizes) * N, device=dmaps.device, dtype=F32)
-            zp = (ctypes.c_void_p * L)(*[z.data_ptr() for z in zs])
-            sp = (ctypes.c_int * L)(*[int(s) for s in sizes])
-            stp = (ctypes.c_void_p * L)(*[st.data_ptr() for st in stats])
-            dp = (ctypes.c_void_p * L)(*[d.data_ptr() for d in dzs])
+            ws = torch.empty(capture_maps_bwd_ws_floats(B, H, N, R, sizes), device=dmaps.device, dtype=F32)
             with _timed("skp_capture_maps_bwd", capture_maps_bwd_bytes(B, H, N, R, sizes),
                         capture_maps_bwd_flops(B, H, N, R, sizes)):
-                call("skp_capture_maps_bwd", ctypes.cast(zp, ctypes.POINTER(ctypes.c_void_p)), sp, L, B, H, N, R,
-                     ptr(dmaps), scale, ctypes.cast(stp, ctypes.POINTER(ctypes.c_void_p)),
-                     ctypes.cast(dp, ctypes.POINTER(ctypes.c_void_p)), ptr(ws), stream(dmaps.device))
-            del ws
+                call("skp_capture_maps_bwd", _layer_ptrs(zs), _layer_sizes(sizes), L, B, H, N, R, ptr(dmaps), scale,
+                     _layer_ptrs(stats), _layer_ptrs(dzs), ptr(ws), stream(dmaps.device))
         else:
             dzs = [capture_bwd(z, s, R, dmaps, gscale=scale, group=H, strides=(N * RR, 1, RR), stats=st)
                    for z, s, st in zip(zs, sizes, stats)]
@@ -496,19 +507,14 @@ def _capture_maps_run(zs, sizes, B, R):
     """skp_capture_maps_fwd: (maps (B, N, R, R), per-layer stats (B·H, R², 2))."""
     zs = [_c16(z) for z in zs]
     BH, _, N = zs[0].shape
-    H = BH // B
-    L = len(zs)
-    dev = zs[0].device
-    RR = R * R
+    H, L = BH // B, len(zs)
+    dev, RR = zs[0].device, R * R
     stats = [torch.empty(BH, RR, 2, device=dev, dtype=F32) for _ in range(L)]
     out = torch.empty(B, N, R, R, device=dev, dtype=F32)
-    zp = (ctypes.c_void_p * L)(*[z.data_ptr() for z in zs])
-    sp = (ctypes.c_int * L)(*[int(s) for s in sizes])
-    stp = (ctypes.c_void_p * L)(*[st.data_ptr() for st in stats])
     with _timed("skp_capture_maps_fwd", capture_maps_bytes(B, H, N, R, sizes), capture_maps_flops(B, H, N, R, sizes),
                 capture_maps_issue_cycles(B, H, N, R, sizes)):
-        call("skp_capture_maps_fwd", ctypes.cast(zp, ctypes.POINTER(ctypes.c_void_p)), sp, L, B, H, N, R,
-             ptr(out), ctypes.cast(stp, ctypes.POINTER(ctypes.c_void_p)), stream(dev))
+        call("skp_capture_maps_fwd", _layer_ptrs(zs), _layer_sizes(sizes), L, B, H, N, R, ptr(out), _layer_ptrs(stats),
+             stream(dev))
     return out, stats
 
 
@@ -517,24 +523,20 @@ def capture_maps_bwd_sel(zs, sizes, B, R, tok_table, gsel, gscale, stats):
     gsel[b, k] (R²) at token tok_table[b, k] (−1 = unused), zero elsewhere (skp_capture_maps_bwd_sel)."""
     zs = [_c16(z) for z in zs]
     BH, _, N = zs[0].shape
-    H = BH // B
-    L = len(zs)
-    K = tok_table.shape[1]
-    dev = zs[0].device
-    sp = (ctypes.c_int * L)(*[int(s) for s in sizes])
+    H, L = BH // B, len(zs)
+    K, dev = tok_table.shape[1], zs[0].device
+    sp = _layer_sizes(sizes)
     nws = _lib.lib().skp_capture_maps_bwd_sel_workspace(sp, L, B, H, N, R, K)
     if nws < 0:
         raise ValueError(f"capture_maps_bwd_sel: bad shape B={B} H={H} N={N} R={R} K={K} sizes={sizes}")
     ws = torch.empty(int(nws), device=dev, dtype=F32)
     dzs = [torch.empty_like(z) for z in zs]
-    arr = lambda ts: ctypes.cast((ctypes.c_void_p * L)(*[t.data_ptr() for t in ts]),   # noqa: E731
-                                 ctypes.POINTER(ctypes.c_void_p))
     tok_table = tok_table.to(device=dev, dtype=torch.int64).contiguous()
     gsel = _c(gsel)
     with _timed("skp_capture_maps_bwd_sel", capture_maps_sel_bwd_bytes(B, H, N, R, sizes, K),
                 capture_maps_sel_bwd_flops(B, H, N, R, sizes), capture_maps_sel_bwd_issue_cycles(B, H, N, R, sizes)):
-        call("skp_capture_maps_bwd_sel", arr(zs), sp, L, B, H, N, R, ptr(tok_table), K, ptr(gsel), float(gscale),
-             arr(stats), arr(dzs), ptr(ws), stream(dev))
+        call("skp_capture_maps_bwd_sel", _layer_ptrs(zs), sp, L, B, H, N, R, ptr(tok_table), K, ptr(gsel),
+             float(gscale), _layer_ptrs(stats), _layer_ptrs(dzs), ptr(ws), stream(dev))
     return dzs
 
 
@@ -546,15 +548,16 @@ class _SelectMaps(torch.autograd.Function):
         B, N, R = cm.B, cm.N, cm.R
         img = torch.cat([torch.full((c,), b, dtype=torch.int64, device=tok.device) for b, c in enumerate(counts) if c]) \
             if tok.numel() else tok
-        out = cm.maps.view(B * N, R * R)[img * N + tok].view(-1, R, R)
+        flat = img * N + tok   # every selected row's index in the (B·N, R²) view of the maps
+        out = cm.maps.view(B * N, R * R)[flat].view(-1, R, R)
         ctx.cm, ctx.counts = cm, counts
-        ctx.save_for_backward(tok)
+        ctx.save_for_backward(tok, flat)
         return out
 
     @staticmethod
     def backward(ctx, g):
         cm, counts = ctx.cm, ctx.counts
-        (tok,) = ctx.saved_tensors
+        tok, flat = ctx.saved_tensors
         B, N, R, L = cm.B, cm.N, cm.R, len(cm.zs)
         RR = R * R
         K = max(max(counts), 1)
@@ -573,8 +576,7 @@ class _SelectMaps(torch.autograd.Function):
             dzs = capture_maps_bwd_sel(cm.zs, cm.sizes, B, R, tt, gs, scale, cm.stats)
         else:
             dense = torch.zeros(B * N, RR, dtype=F32, device=g.device)
-            img = torch.cat([torch.full((c,), b, dtype=torch.int64, device=g.device) for b, c in enumerate(counts) if c])
-            dense.index_add_(0, img * N + tok, g)
+            dense.index_add_(0, flat, g)
             dzs = CaptureMaps._dense_bwd([_c(z) for z in cm.zs], cm.stats, (B, cm.H, R, N, list(cm.sizes)),
                                          dense.view(B, N, R, R))
         cb, cm.after_backward = cm.after_backward, None

@@ -91,10 +91,12 @@ def test_bgemm_layout_identity_asymmetric():
 # ----------------------------------------------------------------------------- A1 capture
 @pytest.mark.parametrize("H,s,R,Nn", [(8, 4, 32, 16), (8, 8, 32, 16), (2, 16, 128, 500), (2, 32, 128, 500),
                                       (3, 5, 13, 70), (1, 16, 128, 1), (1, 16, 256, 40), (1, 8, 32, 1000),
-                                      (2, 1, 8, 20), (1, 32, 16, 9)])
+                                      (2, 1, 8, 20), (1, 32, 16, 9), (1, 4, 16, 256), (1, 4, 16, 257), (1, 4, 16, 512),
+                                      (1, 4, 16, 513), (1, 4, 16, 1024)])
 def test_capture_fwd_vs_oracle(H, s, R, Nn):
     """Includes R=256 (the reference's default feature_upsample_res), N=1000 (its default token
-    count, two tokens per lane), a 1×1 low-res layer and a downsampling R < s."""
+    count, two tokens per lane), a 1×1 low-res layer, a downsampling R < s, and both ends of every
+    token width (1, 2, 4 quads per lane: N up to 256, 512, 1024)."""
     from stablekeypoints_amd import ops
     z = recipes.random_logits(H * 1000 + s, (H, s * s, Nn), scale=3.0)
     got = N(ops.capture_attn(T(z), s, R))
@@ -105,7 +107,8 @@ def test_capture_fwd_vs_oracle(H, s, R, Nn):
 
 
 @pytest.mark.parametrize("H,s,R,Nn", [(8, 4, 32, 16), (2, 16, 128, 500), (2, 32, 128, 300), (3, 5, 13, 70),
-                                      (1, 16, 256, 40), (1, 8, 32, 1000), (2, 1, 8, 20), (1, 32, 16, 9)])
+                                      (1, 16, 256, 40), (1, 8, 32, 1000), (2, 1, 8, 20), (1, 32, 16, 9),
+                                      (1, 4, 16, 512), (1, 4, 16, 513), (1, 4, 16, 1024)])   # 1 | 2 tokens per thread
 def test_capture_bwd_dense_and_broadcast(H, s, R, Nn):
     from stablekeypoints_amd import ops
     z = recipes.random_logits(7 + s, (H, s * s, Nn), scale=2.0)
@@ -674,7 +677,9 @@ def _capture_maps_abi(zs, sizes, B, H, R, with_stats=True):
 @pytest.mark.parametrize("B,H,sizes,R,Nn", [(2, 8, (4, 4, 4, 8), 32, 40), (1, 3, (5, 3), 40, 37), (2, 2, (16, 32), 128, 1),
                                             (1, 2, (8,), 32, 1000), (3, 1, (1, 2), 8, 130), (1, 8, (16, 16, 16, 32), 128, 500),
                                             (1, 4, (7, 13), 100, 256), (1, 2, (6,), 72, 129), (1, 1, (12,), 24, 8),
-                                            (1, 2, (32, 64), 128, 500), (1, 2, (9, 20), 31, 64)])
+                                            (1, 2, (32, 64), 128, 500), (1, 2, (9, 20), 31, 64)]
+                         # both ends of every token width (1, 2, 4, 8, 16 quads per lane) not reached above
+                         + [(1, 1, (4,), 16, n) for n in (65, 128, 257, 512, 513, 1024)])
 def test_capture_maps_fwd_vs_oracle(B, H, sizes, R, Nn):
     """skp_capture_maps_fwd (fused capture + per-image layer/head mean) vs the oracle's
     capture_fwd + collect_maps per image (ptp_utils.py:508-538, optimize.py:27-79): maps within
@@ -752,7 +757,10 @@ def _capture_maps_bwd_abi(zs, sizes, B, H, R, dmaps, gscale, stats):
 @pytest.mark.parametrize("B,H,sizes,R,Nn,with_stats", [(2, 8, (4, 4, 4, 8), 32, 40, True), (1, 3, (5, 3), 40, 36, True),
                                                        (2, 2, (16, 32), 128, 4, False), (1, 2, (8,), 32, 1000, True),
                                                        (3, 1, (1, 2), 8, 128, False), (1, 4, (7, 13), 100, 256, True),
-                                                       (1, 2, (6, 64), 64, 260, True), (2, 4, (16, 32), 128, 500, True)])
+                                                       (1, 2, (6, 64), 64, 260, True), (2, 4, (16, 32), 128, 500, True),
+                                                       # the row kernel's 2 | 4 quads per lane, and its widest N
+                                                       (1, 1, (4,), 16, 512, True), (1, 1, (4,), 16, 516, True),
+                                                       (1, 1, (4,), 16, 1024, True)])
 def test_capture_maps_bwd_vs_oracle(B, H, sizes, R, Nn, with_stats):
     """skp_capture_maps_bwd (one wave per (layer, head, row), V/W windows in registers) vs the
     oracle's capture_bwd of the per-image broadcast gradient (collect_maps_bwd, optimize.py:27-79,

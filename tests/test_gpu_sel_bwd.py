@@ -31,6 +31,7 @@ def _fwd(zs, sizes, B, H, R):
 
 
 def _sel_abi(zs, sizes, B, H, R, tok, gsel, gscale, stats, ws_fill=float("nan")):
+    from stablekeypoints_amd import ops
     from stablekeypoints_amd._lib import call, lib, ptr, stream
     L = len(zs)
     Nn = zs[0].shape[-1]
@@ -40,7 +41,7 @@ def _sel_abi(zs, sizes, B, H, R, tok, gsel, gscale, stats, ws_fill=float("nan"))
     assert nws > 0
     ws = torch.full((nws,), ws_fill, device=DEV)
     dzs = [torch.full_like(z, float("nan")) for z in zs]
-    arr = lambda ts: ctypes.cast((ctypes.c_void_p * L)(*[t.data_ptr() for t in ts]), ctypes.POINTER(ctypes.c_void_p))
+    arr = ops._layer_ptrs
     call("skp_capture_maps_bwd_sel", arr(zs), sp, L, B, H, Nn, R, ptr(tok), K, ptr(gsel), float(gscale), arr(stats),
          arr(dzs), ptr(ws), stream(DEV))
     torch.cuda.synchronize()
@@ -71,6 +72,9 @@ def _case(seed, B, H, sizes, R, Nn, K, dup=False, ragged=False):
     (1, 2, (16,), 32, 20, 2, False, False),               # R = 2·s: dense fallback
     (2, 2, (4, 8, 16), 64, 64, 32, True, True),           # K = 32 (the maximum), three sizes in one launch
     (1, 3, (16, 8, 16, 32), 128, 8, 1, False, False),     # K = 1, N = 8 (one short token chunk), mixed sizes
+    (1, 2, (32, 16), 128, 8, 2, False, False),            # the paired launch with its classes in the other order
+    (1, 1, (16, 16, 16, 16, 16, 32), 128, 8, 2, False, False),   # five equal sizes: three classes, a launch each
+    (1, 2, (8,), 32, 20, 17, False, False),               # 16 < K < 32: the 32-register gradient rows
 ])
 def test_capture_maps_bwd_sel_vs_oracle(B, H, sizes, R, Nn, K, dup, ragged):
     zs, tok, gsel = _case(500 + Nn + R, B, H, sizes, R, Nn, K, dup, ragged)
