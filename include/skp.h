@@ -650,6 +650,48 @@ int skp_match_field_workspace(int B, int n, int P, int Q);
 int skp_match_field(const float* x, long long x_stride, int P, const float* y, long long y_stride, int Q, int B,
                     int n, int* index, float* score, void* workspace, void* stream);
 
+/* Keypoint tracks over a sequence of frames (no reference function: visualize.create_vid takes
+ * find_max_pixel frame by frame): per token the MAP path of a hidden Markov model over the pixel grid,
+ * the emission a frame's TTA average, the transition a truncated Gaussian random walk.  One
+ * skp_track_step per frame, in frame order, then one skp_track_backtrace.
+ *   Per token, frames t = 0 … T−1, a_t (S, S) the frame's average, w[0..r] the caller's table.  Every
+ *   operation fp32 and rounded on its own, no fma:
+ *   frame 0:  m_0 = a_0, back_0 = the centre code everywhere.
+ *   M_t       = max_p m_t(p); best_t = the first row-major index attaining it.
+ *   m̃(q)      = m_{t−1}(q) / M_{t−1}; where M_{t−1} is 0 or not finite (a blank plane) m̃ ≡ 1.0f: the
+ *               track restarts.
+ *   row stage:    g(y', x) = max over dx ∈ [−r, r] with 0 <= x + dx < S of m̃(y', x + dx) · w[|dx|],
+ *                 gdx(y', x) the smallest dx that attains it.
+ *   column stage: h(y, x) = max over dy ∈ [−r, r] with 0 <= y + dy < S of g(y + dy, x) · w[|dy|],
+ *                 dy* the smallest dy that attains it, dx* = gdx(y + dy*, x).
+ *   m_t(y, x)    = a_t(y, x) · h(y, x);   back_t(y, x) = (dy* + r)·(2r + 1) + (dx* + r), int16.
+ *   The two stages are the definition: a one-stage maximum over (dy, dx) has the same value (the
+ *   Gaussian is a product of one factor per axis) but can break ties inside a row differently.
+ *   A back-pointer always names a pixel of the plane.  Planes that hold NaN, an infinity or a
+ *   negative value give that token unspecified tracks, never a back-pointer outside the plane.
+ *   Backtrace: p_{T−1} = best_{T−1}, p_{t−1} = p_t + the (dy, dx) that back_t(p_t) encodes;
+ *   pos[t, j] = (row + 0.5, col + 0.5) of p_t, skp_argmax2d's convention.
+ * skp_track_step: avg, prev_score, score (n, S, S); prev_max, score_max (n); best (n) int32; back
+ *   (n, S, S) int16.  prev_score and prev_max are null together for frame 0.  w_host: r + 1 floats in
+ *   HOST memory, read during the call and passed to the kernel by value.  Two launches, no atomics:
+ *   the tile kernel (one workgroup per token and 32 × 32 pixels: the tile of prev_score and its halo
+ *   of r to LDS, divided on the way in; the row stage to LDS; the column stage from it; times avg)
+ *   leaves one (max, first index) partial per tile, and the merge takes each token's.  Deterministic.
+ *   workspace: skp_track_step_workspace(n, S, r) bytes (−1 on a bad shape, or at 2^31 bytes), 8-B
+ *   aligned: 2·r8(4·n·tiles), tiles = ⌈S / 32⌉².
+ * skp_track_backtrace: back (T, n, S, S) — the steps' back planes in frame order; best_last (n) the
+ *   last step's best; pos (T, n, 2).  One launch, one thread per token walks the T dependent loads.  A
+ *   code or an index outside its range (a buffer the steps did not write) is clamped into it.
+ * Rejected before any launch: a null pointer, except the frame-0 pair; exactly one of prev_score and
+ * prev_max null; n, S or T below 1; S > 4096; n > 65535 (the step); r outside [1, 32]; a weight that is
+ * not finite or not in (0, 1].                                                                   */
+int skp_track_step_workspace(int n, int S, int r);
+int skp_track_step(const float* avg, const float* prev_score, const float* prev_max, int n, int S,
+                   const float* w_host, int r, float* score, float* score_max, int* best, short* back,
+                   void* workspace, void* stream);
+int skp_track_backtrace(const short* back, const int* best_last, int T, int n, int S, int r, float* pos,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

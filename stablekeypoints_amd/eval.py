@@ -23,6 +23,9 @@ pixel whose signature has the greatest cosine with it.
 ``match_images`` (extra) matches EVERY pixel of unlabelled images against a source image and back
 (``skp_match_field``, the (S², S²) product never in memory); ``transfer_labels`` and
 ``transfer_points_dense`` read masks, part segmentations and any number of points off that field.
+``track_keypoints`` and ``track_images`` (extra) turn the per-frame TTA averages of a video into one
+track per token: exact Viterbi over the pixel grid under a truncated Gaussian random walk, a fused
+separable max-product per frame (``skp_track_step``) and one walk back (``skp_track_backtrace``).
 """
 import collections
 import contextlib
@@ -816,3 +819,137 @@ def transfer_points_dense(match, points):
     pos = torch.stack([hit.clamp_min(0) // S, hit.clamp_min(0) % S], dim=-1).to(torch.float32) / S
     pos = torch.where(ok[..., None], pos, torch.full_like(pos, float("nan")))
     return pos, torch.where(ok, sc, torch.full_like(sc, float("-inf")))
+
+
+KeypointTracks = collections.namedtuple("KeypointTracks", ["pos", "support", "independent"])
+
+
+class _Tracker:
+    """The frames of one sequence, one ``push`` per frame in order, then ``finish``.  Holds the int16
+    back-pointers of every frame (one (T, n, S, S) stack where the frame count is known beforehand, else
+    a plane per frame that ``finish`` stacks), the last frame's state and, while a step runs, the new
+    score plane beside the previous one; per frame besides that only each token's own argmax and peak."""
+
+    def __init__(self, weights, device, frames=None):
+        self.w, self.r, self.device = weights, weights.numel() - 1, torch.device(device)
+        self.T, self.t, self.state, self.stack, self.backs, self.own, self.peak = frames, 0, None, None, [], [], []
+
+    def push(self, frame):
+        a = torch.as_tensor(frame)
+        if a.dim() != 3 or a.shape[-1] != a.shape[-2]:
+            raise ValueError(f"a frame must be (n, S, S), got {tuple(a.shape)}")
+        a = a.to(self.device, torch.float32).contiguous()
+        if self.t == 0:
+            self.n, self.S = a.shape[0], a.shape[-1]
+            if self.T is not None:
+                self.stack = torch.empty(self.T, self.n, self.S, self.S, device=self.device, dtype=torch.int16)
+        elif tuple(a.shape) != (self.n, self.S, self.S):
+            raise ValueError(f"frame {self.t} is {tuple(a.shape)}, frame 0 was {(self.n, self.S, self.S)}")
+        if self.stack is not None and self.t >= self.T:
+            raise ValueError(f"more than the {self.T} frames announced")
+        self.state = ops.track_step(a, self.state, self.w, back=None if self.stack is None else self.stack[self.t])
+        if self.stack is None:
+            self.backs.append(self.state[3])
+        own = ops.argmax_index(a)
+        self.own.append(own)
+        self.peak.append(a.reshape(self.n, -1).gather(1, own[:, None])[:, 0])
+        self.t += 1
+
+    def finish(self, frames):
+        """``frames``: the pushed frames once more, in order (a (T, n, S, S) tensor or an iterable of
+        (n, S, S) frames, on any device): only the tracked pixel of each plane is read."""
+        if self.t < 1:
+            raise ValueError("at least one frame is needed")
+        if self.stack is not None and self.t != self.T:
+            raise ValueError(f"{self.t} frames came, {self.T} were announced")
+        T, n, S = self.t, self.n, self.S
+        stack = self.stack if self.stack is not None else torch.stack(self.backs)
+        self.backs = []
+        pos = ops.track_backtrace(stack, self.state[2], self.r)               # (T, n, 2), pixel centres
+        flat = pos[..., 0].long() * S + pos[..., 1].long()                    # (T, n)
+        if torch.is_tensor(frames):
+            at = frames.reshape(T, n, S * S).gather(2, flat.to(frames.device)[..., None])[..., 0]
+        else:
+            flat_cpu, at = flat.cpu(), []
+            for t, f in enumerate(frames):
+                f = torch.as_tensor(f).reshape(n, S * S)
+                at.append(f.gather(1, (flat[t] if f.is_cuda else flat_cpu[t])[:, None])[:, 0].to(self.device))
+            at = torch.stack(at)
+        # the three quotients on the host: one IEEE division each, whatever device the frames were on
+        at, peak = at.to(torch.float32).cpu(), torch.stack(self.peak).cpu()
+        live = (peak != 0) & torch.isfinite(peak)
+        support = torch.where(live, at / torch.where(live, peak, torch.ones_like(peak)), torch.zeros_like(at))
+        own = torch.stack(self.own).cpu()
+        independent = torch.stack([own // S, own % S], dim=-1).to(torch.float32) + 0.5
+        size = torch.tensor(float(S))
+        return KeypointTracks((pos.cpu() / size).to(self.device), support.to(self.device),
+                              (independent / size).to(self.device))
+
+
+@torch.no_grad()
+def track_keypoints(maps, sigma=2.0, radius=None, device="cuda"):
+    """Keypoint tracks over a video from its per-frame TTA averages (extra: ``visualize.create_vid``
+    takes ``find_max_pixel`` frame by frame, and a per-frame argmax jumps whenever a second mode of a
+    token's map briefly wins).  Per token the track is the MAP path of a hidden Markov model over the
+    pixel grid: the emission is the frame's average, the transition a Gaussian random walk of
+    ``sigma`` pixels truncated at ``radius`` (``ops.track_weights``; default ``ceil(3·sigma)`` clipped
+    to [1, 32]).  Exact Viterbi, one ``ops.track_step`` per frame and one ``ops.track_backtrace``.
+
+    ``maps`` is a (T, n, S, S) tensor or any iterable of (n, S, S) frames in frame order: what
+    ``predict_keypoints(return_maps=True)`` returns, or the list that ``create_vid`` saved in
+    ``saved_maps.pt``.  CPU frames are uploaded to ``device`` one at a time (a tensor on a HIP device
+    stays where it is); an iterable without a length is first made a list.  Only the int16
+    back-pointers of all frames and two score planes are held besides the caller's frames, which are
+    read once more at the tracked pixels.
+
+    Returns ``KeypointTracks(pos, support, independent)``: ``pos`` (T, n, 2) the track's (row, col) =
+    position / S; ``support`` (T, n) the frame's average at the tracked pixel over that average's
+    maximum, 1 where the track agrees with the frame's own peak and 0 where the plane is blank;
+    ``independent`` (T, n, 2) the per-frame argmax / S, for comparison.  Planes that hold NaN, an
+    infinity or a negative value give that token unspecified tracks.
+    """
+    weights = ops.track_weights(sigma, radius)
+    if torch.is_tensor(maps):
+        if maps.dim() != 4:
+            raise ValueError(f"maps must be (T, n, S, S) or an iterable of (n, S, S) frames, got {tuple(maps.shape)}")
+        if maps.is_cuda:
+            device = maps.device
+    elif not hasattr(maps, "__len__"):
+        maps = list(maps)
+    if len(maps) < 1:
+        raise ValueError("at least one frame is needed")
+    tracker = _Tracker(weights, device, len(maps))
+    for frame in maps:
+        tracker.push(frame)
+    return tracker.finish(maps)
+
+
+@torch.no_grad()
+def track_images(ldm, images, context, indices, device="cuda", layers=(0, 1, 2, 3, 4, 5), noise_level=-1,
+                 augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1), augmentation_iterations=20,
+                 controllers=None, upscale_size=128, image_batch=None, sigma=2.0, radius=None):
+    """``track_keypoints`` of the frames of a video: ``images`` (T, 3, H, W) in [0, 1], in frame order.
+
+    The thetas are drawn and the passes captured as ``predict_keypoints`` does (``_tta_passes``); each
+    pass's averages, from ``ops.tta_reduce(return_avg=True)``, are fed to the tracker frame by frame as
+    they come and then kept on the host for the read at the tracked pixels, so no more than one pass
+    of captured maps and one pass of averages is on the device at a time.  The result is what
+    ``track_keypoints`` gives on ``predict_keypoints(..., return_maps=True)``'s maps from the same
+    seed, bit for bit.  Single process only: under a process group of more than one rank it raises.
+    """
+    C, S = int(augmentation_iterations), int(upscale_size)
+    indices = _tokens_of(indices, context, C, S, "track")
+    weights = ops.track_weights(sigma, radius)
+    imgs = torch.as_tensor(images)
+    tracker = _Tracker(weights, device, imgs.shape[0] if imgs.dim() == 4 else 1)
+    kept = []
+    for _, nb, maps, th_inv in _tta_passes("track_images", ldm, imgs, context, indices, device, layers, noise_level,
+                                           augment_degrees, augment_scale, augment_translate, C, controllers, S,
+                                           image_batch):
+        _, avg = ops.tta_reduce(maps, th_inv, return_avg=True)
+        del maps
+        for b in range(nb):
+            tracker.push(avg[b])
+        kept.append(avg.cpu())
+        del avg
+    return tracker.finish([f for a in kept for f in a])

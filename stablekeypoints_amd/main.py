@@ -22,7 +22,10 @@ image (``eval.describe_points`` and ``eval.transfer_keypoints`` at ``--transfer_
 are the dataset's, and with ``--visualize`` ``transfer.png``).  With ``--dense_transfer SRC`` it also matches every pixel of
 every image against the dataset's first image and carries that image's labels over (``eval.match_images`` and
 ``eval.transfer_labels`` at ``--dense_size``: ``dense_index.pt``, ``dense_score.pt``, ``dense_cycle.pt``, ``dense_labels.pt``,
-``dense_fg_iou.pt`` where the dataset has foreground masks, and with ``--visualize`` ``dense.png``).  With ``--visualize``,
+``dense_fg_iou.pt`` where the dataset has foreground masks, and with ``--visualize`` ``dense.png``).  With ``--track`` the
+dataset's items in index order are the frames of a video and it also writes one track per token (``eval.track_images`` at
+``--track_size``, ``--track_sigma`` and ``--track_radius``: ``tracked_keypoints.pt``, ``track_support.pt``,
+``tracked_keypoints.csv``, and with ``--visualize`` ``track.png``).  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -139,6 +142,15 @@ def build_parser():
                    help="--dense_transfer: no label where the match does not come back within this many pixels")
     p.add_argument("--dense_min_score", type=float, default=None,
                    help="--dense_transfer: no label where the match's cosine is below this")
+    p.add_argument("--track", action="store_true",
+                   help="predict stage only: the dataset's items in index order are the frames of a video; also write one "
+                        "track per token, the most probable path of its TTA averages' peak under a Gaussian random walk "
+                        "(tracked_keypoints.pt (M, n, 2), track_support.pt (M, n), tracked_keypoints.csv)")
+    p.add_argument("--track_sigma", type=float, default=2.0,
+                   help="--track: standard deviation of the walk's step, in pixels of --track_size")
+    p.add_argument("--track_radius", type=int, default=None,
+                   help="--track: the longest step per frame and axis, 1 to 32 pixels (default ceil(3 sigma), clipped)")
+    p.add_argument("--track_size", type=int, default=128, help="--track: side S of the averages that are tracked")
     return p
 
 
@@ -398,6 +410,36 @@ def dense_stage(args, ldm, controllers, embedding, indices, dataset):
               f"{os.path.join(folder, 'dense_labels.pt')}", flush=True)
 
 
+def track_stage(args, ldm, controllers, embedding, indices, dataset):
+    """``--track``: the dataset's items in index order are the frames of a video.  ``eval.track_images`` tracks the
+    prediction's tokens through them at ``--track_size`` with ``--track_sigma`` and ``--track_radius``.  Writes
+    ``tracked_keypoints.pt`` (M, n, 2) = (row, col) / S, ``track_support.pt`` (M, n) (each frame's average at the
+    tracked pixel over its maximum) and ``tracked_keypoints.csv`` (no header: index, file name where the reader has
+    one, the n (row, col) pairs, then the n supports); with ``--visualize`` ``track.png``, the first 12 frames at most
+    in one row with their tracked points.  The CPU and device RNG states are what they were on entry when it returns,
+    so the prediction that follows draws what a plain predict run draws."""
+    from .eval import track_images
+    folder, M = args.save_folder, len(dataset)
+    if M < 1:
+        raise ValueError("--track: the dataset is empty")
+    with _rng_restored(args.device):
+        images = torch.stack([torch.as_tensor(dataset[i]["img"]) for i in range(M)])
+        tracks = track_images(ldm, images, embedding, indices.cpu(), device=args.device, layers=args.layers,
+                              noise_level=args.noise_level, augment_degrees=args.augment_degrees,
+                              augment_scale=args.augment_scale, augment_translate=args.augment_translate,
+                              augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                              upscale_size=args.track_size, sigma=args.track_sigma, radius=args.track_radius)
+        pos, support = tracks.pos.cpu(), tracks.support.cpu()
+        torch.save(pos, os.path.join(folder, "tracked_keypoints.pt"))
+        torch.save(support, os.path.join(folder, "track_support.pt"))
+        _write_rows(os.path.join(folder, "tracked_keypoints.csv"), _image_names(dataset),
+                    torch.cat([pos.flatten(1), support], dim=1))
+        if args.visualize:
+            _save_row_sheet(os.path.join(folder, "track.png"), images, tracks.pos, args.device)
+        print(f"track: {M} frames, {pos.shape[1]} tokens at {args.track_size} -> "
+              f"{os.path.join(folder, 'tracked_keypoints.pt')}", flush=True)
+
+
 def predict_stage(args, ldm, controllers, batch=4):
     """``--start_from_stage predict``: the keypoints of every image of the dataset (built as
     ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
@@ -416,7 +458,8 @@ def predict_stage(args, ldm, controllers, batch=4):
     ``indices.pt``, and ``regressor.pt`` is not applied (it was fitted to other tokens).
     With ``--part_maps`` ``parts_stage`` first writes the part maps of the same images; the keypoints are
     the same bits with and without it.  With ``--transfer K`` ``transfer_stage`` does the same for the transferred
-    landmarks, and with ``--dense_transfer SRC`` ``dense_stage`` for the dense field and the transferred labels."""
+    landmarks, with ``--dense_transfer SRC`` ``dense_stage`` for the dense field and the transferred labels, and with
+    ``--track`` ``track_stage`` for the tokens' tracks through the images as frames."""
     from .datasets import make_dataset
     from .eval import predict_keypoints
     folder = args.save_folder
@@ -438,6 +481,8 @@ def predict_stage(args, ldm, controllers, batch=4):
         transfer_stage(args, ldm, controllers, embedding, indices, dataset)
     if args.dense_transfer is not None:
         dense_stage(args, ldm, controllers, embedding, indices, dataset)
+    if args.track:
+        track_stage(args, ldm, controllers, embedding, indices, dataset)
     names = _image_names(dataset)
     k = int(args.num_subjects)
     kps, regs, scos, refs, pks, vals = [], [], [], [], [], []
@@ -517,6 +562,14 @@ def main(argv=None):
         parser.error("--dense_transfer belongs to --start_from_stage predict")
     if args.dense_size < 2:
         parser.error("--dense_size must be at least 2")
+    if args.track and args.start_from_stage != "predict":
+        parser.error("--track belongs to --start_from_stage predict")
+    if args.track_size < 2:
+        parser.error("--track_size must be at least 2")
+    if not 0.0 < args.track_sigma < float("inf"):
+        parser.error("--track_sigma must be positive and finite")
+    if args.track_radius is not None and not 1 <= args.track_radius <= 32:
+        parser.error("--track_radius must be in [1, 32]")
     from .launch import launcher_env, spawn_ranks
     # torch.cuda.device_count() does not initialise HIP on this image, so the ranks can still start
     n = ranks_to_start(args, torch.cuda.device_count(), launcher_env())

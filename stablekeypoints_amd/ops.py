@@ -2422,3 +2422,102 @@ def match_field(x, y):
         call("skp_match_field", ptr(x), n * P if bx == B and B > 1 else 0, P, ptr(y), n * Q if by == B and B > 1 else 0,
              Q, B, n, ptr(index), ptr(score), ptr(ws), stream(dev))
     return index, score
+
+
+# --------------------------------------------------------------------------- A20 keypoint tracks
+def track_weights(sigma, radius=None):
+    """The transition table of ``track_step``: ``w[k] = exp(−k² / (2σ²))`` for k = 0 … radius, evaluated
+    in double on the host and rounded once to float32 (a CPU tensor; ``w[0] == 1``).  ``radius=None`` is
+    ``ceil(3σ)`` clipped to [1, 32]; a given radius must lie in [1, 32].  A table whose last entry
+    rounds to 0 is refused (the kernel takes weights in (0, 1]): lower the radius or raise sigma."""
+    import math
+    s = float(sigma)
+    if not 0.0 < s < float("inf"):
+        raise ValueError(f"track_weights: sigma must be positive and finite, got {s}")
+    r = min(max(int(math.ceil(3.0 * s)), 1), 32) if radius is None else int(radius)
+    if not 1 <= r <= 32:
+        raise ValueError(f"track_weights: radius must be in [1, 32], got {r}")
+    w = torch.tensor([math.exp(-(k * k) / (2.0 * s * s)) for k in range(r + 1)], dtype=torch.float64).to(F32)
+    if not float(w[-1]) > 0.0:
+        raise ValueError(f"track_weights: exp(-{r}^2 / (2 * {s}^2)) rounds to 0 in float32: lower the radius")
+    return w
+
+
+def track_step_bytes(n, S):
+    """Byte model of skp_track_step: per pixel three planes of 4 bytes (the average and the previous
+    score read, the score written) and one of 2 (the back-pointer).  The halo's re-reads are cache
+    traffic."""
+    return (3 * 4 + 2) * n * S * S
+
+
+def track_step(avg, state=None, weights=None, back=None):
+    """One frame of the keypoint tracker (skp_track_step): the Viterbi step of include/skp.h, per token
+    an exact max-product over the (2r + 1)² window in two separable stages from an LDS tile.
+
+    ``avg`` (n, S, S): the frame's TTA averages, float32, contiguous, on the device.  ``state``: what
+    the previous frame's call returned, None for frame 0.  ``weights``: the float32 CPU table of
+    ``track_weights`` (r + 1 entries, r in [1, 32]).  ``back``: an (n, S, S) int16 contiguous buffer
+    to write the back-pointers into (a slice of the caller's (T, n, S, S) stack), else a new one.
+    Returns the state ``(score (n, S, S), score_max (n), best (n) int32, back (n, S, S) int16)``.
+    """
+    _lib.require_device(avg)
+    if avg.dim() != 3 or avg.shape[-1] != avg.shape[-2]:
+        raise ValueError(f"track_step: avg must be (n, S, S), got {tuple(avg.shape)}")
+    if avg.dtype != F32:
+        raise ValueError(f"track_step: avg must be float32, got {avg.dtype}")
+    if not avg.is_contiguous():
+        raise ValueError(f"track_step: avg must be contiguous, got strides {avg.stride()}")
+    if (not torch.is_tensor(weights) or weights.is_cuda or weights.dtype != F32 or weights.dim() != 1
+            or not weights.is_contiguous() or not 2 <= weights.numel() <= 33):
+        raise ValueError("track_step: weights must be the float32 CPU table of track_weights (2 to 33 entries)")
+    n, S, _ = avg.shape
+    r, dev = weights.numel() - 1, avg.device
+    prev, prev_max = (None, None) if state is None else (state[0], state[1])
+    for name, t, shape in (("state's score", prev, (n, S, S)), ("state's score_max", prev_max, (n,))):
+        if t is None:
+            continue
+        if tuple(t.shape) != shape or t.dtype != F32 or not t.is_contiguous():
+            raise ValueError(f"track_step: the {name} must be {shape} float32 contiguous, got {tuple(t.shape)} {t.dtype}")
+        if t.device != dev:
+            raise ValueError(f"track_step: the {name} on {t.device}, avg on {dev}")
+    if back is None:
+        back = torch.empty(n, S, S, device=dev, dtype=torch.int16)
+    elif (tuple(back.shape) != (n, S, S) or back.dtype != torch.int16 or not back.is_contiguous()
+          or back.device != dev):
+        raise ValueError(f"track_step: back must be ({n}, {S}, {S}) int16 contiguous on {dev}")
+    key = ("track_step", dev, n, S, r)
+    ws = _TTA_WS.get(key)
+    if ws is None:
+        nbytes = _lib.lib().skp_track_step_workspace(n, S, r)
+        if nbytes <= 0:
+            raise ValueError(f"track_step: bad shape n={n}, S={S}, r={r}")
+        ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    score = torch.empty(n, S, S, device=dev, dtype=F32)
+    score_max = torch.empty(n, device=dev, dtype=F32)
+    best = torch.empty(n, device=dev, dtype=torch.int32)
+    with _timed("skp_track_step", track_step_bytes(n, S)):
+        call("skp_track_step", ptr(avg), ptr(prev), ptr(prev_max), n, S, ctypes.c_void_p(weights.data_ptr()), r,
+             ptr(score), ptr(score_max), ptr(best), ptr(back), ptr(ws), stream(dev))
+    return score, score_max, best, back
+
+
+def track_backtrace(back_stack, best_last, radius):
+    """The tracks of ``track_step``'s frames (skp_track_backtrace): ``back_stack`` (T, n, S, S) int16 the
+    frames' back-pointers in frame order, ``best_last`` (n) int32 the last frame's ``best``, ``radius``
+    the steps'.  Returns ``pos`` (T, n, 2) = (row + 0.5, col + 0.5) of the path's pixel in every frame."""
+    _lib.require_device(back_stack, best_last)
+    if back_stack.dim() != 4 or back_stack.shape[-1] != back_stack.shape[-2] or back_stack.dtype != torch.int16:
+        raise ValueError(f"track_backtrace: back_stack must be (T, n, S, S) int16, got {tuple(back_stack.shape)} "
+                         f"{back_stack.dtype}")
+    if not back_stack.is_contiguous():
+        raise ValueError(f"track_backtrace: back_stack must be contiguous, got strides {back_stack.stride()}")
+    T, n, S, _ = back_stack.shape
+    if tuple(best_last.shape) != (n,) or best_last.dtype != torch.int32 or not best_last.is_contiguous():
+        raise ValueError(f"track_backtrace: best_last must be ({n},) int32, got {tuple(best_last.shape)} {best_last.dtype}")
+    if best_last.device != back_stack.device:
+        raise ValueError(f"track_backtrace: best_last on {best_last.device}, back_stack on {back_stack.device}")
+    dev = back_stack.device
+    pos = torch.empty(T, n, 2, device=dev, dtype=F32)
+    with _timed("skp_track_backtrace", 2 * T * n + 8 * T * n + 4 * n):
+        call("skp_track_backtrace", ptr(back_stack), ptr(best_last), T, n, S, int(radius), ptr(pos), stream(dev))
+    return pos
