@@ -650,6 +650,36 @@ int skp_match_field_workspace(int B, int n, int P, int Q);
 int skp_match_field(const float* x, long long x_stride, int P, const float* y, long long y_stride, int Q, int B,
                     int n, int* index, float* score, void* workspace, void* stream);
 
+/* The windowed refine of a coarse field (no reference function: coarse-to-fine dense matching): for
+ * every pixel p of X's S × S grid the best pixel q of Y's grid inside a (2w + 1)² window whose centre
+ * a coarse field gives, one prior per f × f cell of X's grid.  With f = 1 it re-matches around any
+ * prior field.
+ *   x, y, x_stride, y_stride, index (B, S²) int32 and score (B, S²) float32: skp_match_field's with
+ *   P = Q = S², token-major (n, S²), a stride of 0 one operand shared by the B images.
+ *   coarse (B, Sc²) int32, Sc = S / f: per cell of X's grid a cell of Y's grid, row·Sc + col.
+ *   Per image, every operation fp32 and rounded on its own:
+ *   nx, ny, usable, rx, ry, dot[p,q] (the fmaf chain in token order, one accumulator per (p, q), no
+ *   split over the tokens) and key[p,q] = dot · ry[q], a NaN key counting as −inf, are skp_match_field's
+ *   word for word: a key here is bit for bit the key there.
+ *   Window: for p = (r, c), m = coarse[b, (r / f)·Sc + c / f]; p has no prior where m < 0 or m >= Sc².
+ *               (cr, cc) = ((m / Sc)·f + r % f, (m % Sc)·f + c % f); W(p) = every q = (qr, qc) of the
+ *               plane with |qr − cr| <= w and |qc − cc| <= w: clipped at the borders, never empty.
+ *   index[p]  = the lowest usable q in W(p) with the greatest key;  score[p] = that key · rx[p];
+ *               −1 and −inf where p is not usable, where p has no prior, or where no q in W(p) is
+ *               usable.  Nothing outside the two planes is read, whatever coarse holds.
+ * A result depends neither on how pixels are grouped into workgroups nor on the image's place in the
+ * batch.  One launch, no atomics: one workgroup per image and cell takes the (f + 2w)² region of y that
+ * the cell's windows share through LDS in passes, a register-blocked fmaf kernel with the norms
+ * riding along and the (key, q) fold in registers.  Two runs give the same bits.
+ * workspace: skp_match_refine_workspace(B, n, S, f, w) bytes (−1 on a bad shape, or at 2^31 bytes),
+ * 8-B aligned: 8 — the kernel keeps nothing in memory, no copy of y and nothing of the order of
+ * S²·(2w + 1)²; the pointer is checked and otherwise unused.
+ * Rejected before any launch: a null pointer; B, n or S below 1; n > 4096; S > 1024; f outside [1, 8]
+ * or S % f != 0; w outside [1, 16]; a non-zero stride below n·S²; B·Sc² of 2^31 or more.          */
+int skp_match_refine_workspace(int B, int n, int S, int f, int w);
+int skp_match_refine(const float* x, long long x_stride, const float* y, long long y_stride, int B, int n, int S,
+                     const int* coarse, int f, int w, int* index, float* score, void* workspace, void* stream);
+
 /* Keypoint tracks over a sequence of frames (no reference function: visualize.create_vid takes
  * find_max_pixel frame by frame): per token the MAP path of a hidden Markov model over the pixel grid,
  * the emission a frame's TTA average, the transition a truncated Gaussian random walk.  One

@@ -114,6 +114,8 @@ _SIGS = {
     "skp_tta_reduce_match": [_p, _c_int, _c_int, _c_int, _c_int, _p, _p, _c_int, _p, _p, _p, _p, _p, _p, _p],
     "skp_match_field_workspace": [_c_int, _c_int, _c_int, _c_int],
     "skp_match_field": [_p, _c_ll, _c_int, _p, _c_ll, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "skp_match_refine_workspace": [_c_int, _c_int, _c_int, _c_int, _c_int],
+    "skp_match_refine": [_p, _c_ll, _p, _c_ll, _c_int, _c_int, _c_int, _p, _c_int, _c_int, _p, _p, _p, _p],
     "skp_track_step_workspace": [_c_int, _c_int, _c_int],
     "skp_track_step": [_p, _p, _p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _p, _p, _p],
     "skp_track_backtrace": [_p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p],

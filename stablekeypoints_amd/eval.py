@@ -21,7 +21,8 @@ over to unlabelled ones: at a pixel the tokens' TTA averages are a signature, an
 signature is its landmark's descriptor, and ``skp_tta_reduce_match`` finds in every other image the
 pixel whose signature has the greatest cosine with it.
 ``match_images`` (extra) matches EVERY pixel of unlabelled images against a source image and back
-(``skp_match_field``, the (S², S²) product never in memory); ``transfer_labels`` and
+(``skp_match_field``, the (S², S²) product never in memory; with ``coarse_size`` coarse to fine, the
+fine pixels matched inside windows around a coarse field by ``skp_match_refine``); ``transfer_labels`` and
 ``transfer_points_dense`` read masks, part segmentations and any number of points off that field.
 ``track_keypoints`` and ``track_images`` (extra) turn the per-frame TTA averages of a video into one
 track per token: exact Viterbi over the pixel grid under a truncated Gaussian random walk, a fused
@@ -717,7 +718,8 @@ def _cycle_distance(index, back_index, S):
 @torch.no_grad()
 def match_images(ldm, source, images, context, indices=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
                  noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
-                 augmentation_iterations=20, controllers=None, upscale_size=128, image_batch=None):
+                 augmentation_iterations=20, controllers=None, upscale_size=128, image_batch=None, coarse_size=None,
+                 refine_radius=None):
     """The dense field between one source image and unlabelled images (extra: everything an exemplar
     carries — a mask, a part segmentation, any number of points — transfers through one operation: for
     every pixel of one image the pixel of the other whose signature, the n tokens' TTA averages, has
@@ -728,6 +730,15 @@ def match_images(ldm, source, images, context, indices=None, device="cuda", laye
     them; every pass is reduced by ``ops.tta_reduce(..., return_avg=True)`` and the source's averages
     are kept for the whole call.  Per pass two ``ops.match_field`` calls: the images' pixels against
     the source's, and the source's pixels against each image's.
+
+    ``coarse_size=Sc`` matches coarse to fine instead: Sc divides S by f = S / Sc in [2, 8]; the passes and
+    the draws are the same.  The coarse signatures are ``avg_pool2d(avg, f)`` of the fine averages, of
+    the source and of the images; the coarse fields come from ``ops.match_field`` on them, in both
+    directions, and the fine fields from ``ops.match_refine``, which matches every pixel inside a window
+    of ``refine_radius`` pixels (default f + 1, at most 16: a correct coarse match places the window's
+    centre within f of the true match on each axis) around its cell's coarse match.  The result is at
+    S, ``cycle`` on the fine fields; a fine pixel whose cell has no coarse match gets −1 and −inf.  How
+    well refined fields agree with brute-force ones on real images has not been measured.
 
     Returns ``DenseMatch(index, score, back_index, back_score, cycle, token_points)``, the first five
     (M, S, S) with S = ``upscale_size``: ``index`` int32 the source pixel (row · S + col) matched to
@@ -744,20 +755,44 @@ def match_images(ldm, source, images, context, indices=None, device="cuda", laye
     src = torch.as_tensor(source)
     if src.dim() != 3 or src.shape[0] != 3:
         raise ValueError(f"source must be (3, H, W), got {tuple(src.shape)}")
+    f = w = None
+    if coarse_size is not None:
+        Sc = int(coarse_size)
+        if Sc < 1 or S % Sc != 0 or not 2 <= S // Sc <= 8:
+            raise ValueError(f"coarse_size must divide upscale_size = {S} by a factor in [2, 8], got {coarse_size}")
+        f = S // Sc
+        w = f + 1 if refine_radius is None else int(refine_radius)
+        if not 1 <= w <= 16:
+            raise ValueError(f"refine_radius must be in [1, 16], got {w}")
+    elif refine_radius is not None:
+        raise ValueError("refine_radius belongs to coarse_size")
+
+    def both_ways(avg, nb):
+        """(index, score, back_index, back_score), each (nb, S²), of ``avg`` (nb, n, S, S) and the source."""
+        if f is None:
+            sig = avg.reshape(nb, n, S * S)
+            return ops.match_field(sig, src_sig) + ops.match_field(src_sig, sig)
+        low = torch.nn.functional.avg_pool2d(avg, f).contiguous()
+        there, _ = ops.match_field(low.reshape(nb, n, Sc * Sc), src_low.reshape(1, n, Sc * Sc))
+        back, _ = ops.match_field(src_low.reshape(1, n, Sc * Sc), low.reshape(nb, n, Sc * Sc))
+        got = (ops.match_refine(avg, src_avg, there.reshape(nb, Sc, Sc), w)
+               + ops.match_refine(src_avg, avg, back.reshape(nb, Sc, Sc), w))
+        return tuple(t.reshape(nb, S * S) for t in got)
+
     common = (noise_level, augment_degrees, augment_scale, augment_translate, C, controllers, S)
     src_avg = None
     for _, _, maps, th_inv in _tta_passes("match_images", ldm, src, context, indices, device, layers, *common, 1):
         _, src_avg = ops.tta_reduce(maps, th_inv, return_avg=True)
         del maps
     src_sig = src_avg.reshape(1, n, S * S)
+    src_low = None if f is None else torch.nn.functional.avg_pool2d(src_avg, f).contiguous()
     pos, fields = [], ([], [], [], [])
     for _, nb, maps, th_inv in _tta_passes("match_images", ldm, images, context, indices, device, layers, *common,
                                            image_batch):
         p, avg = ops.tta_reduce(maps, th_inv, return_avg=True)
         del maps
-        sig = avg.reshape(nb, n, S * S)
-        got = ops.match_field(sig, src_sig) + ops.match_field(src_sig, sig)
-        del avg, sig
+        got = both_ways(avg.reshape(nb, n, S, S), nb)
+        del avg
         pos.append(p)
         for acc, t in zip(fields, got):
             acc.append(t)

@@ -21,7 +21,8 @@ image (``eval.describe_points`` and ``eval.transfer_keypoints`` at ``--transfer_
 ``transferred_keypoints.pt``, ``transfer_scores.pt``, ``transferred_keypoints.csv``, ``transfer_error.pt`` where the annotations
 are the dataset's, and with ``--visualize`` ``transfer.png``).  With ``--dense_transfer SRC`` it also matches every pixel of
 every image against the dataset's first image and carries that image's labels over (``eval.match_images`` and
-``eval.transfer_labels`` at ``--dense_size``: ``dense_index.pt``, ``dense_score.pt``, ``dense_cycle.pt``, ``dense_labels.pt``,
+``eval.transfer_labels`` at ``--dense_size``, with ``--dense_coarse SC`` and ``--dense_radius W`` coarse to fine:
+a field at SC refined inside windows at ``--dense_size``: ``dense_index.pt``, ``dense_score.pt``, ``dense_cycle.pt``, ``dense_labels.pt``,
 ``dense_fg_iou.pt`` where the dataset has foreground masks, and with ``--visualize`` ``dense.png``).  With ``--track`` the
 dataset's items in index order are the frames of a video and it also writes one track per token (``eval.track_images`` at
 ``--track_size``, ``--track_sigma`` and ``--track_radius``: ``tracked_keypoints.pt``, ``track_support.pt``,
@@ -136,6 +137,14 @@ def build_parser():
                         "mask: foreground 0, background -1) or a saved integer tensor of labels for the source, -1 = "
                         "unlabelled, nearest-resized to --dense_size")
     p.add_argument("--dense_size", type=int, default=128, help="--dense_transfer: side S of the averages that are matched")
+    p.add_argument("--dense_coarse", type=int, default=None, metavar="SC",
+                   help="--dense_transfer: coarse to fine.  The averages, pooled to SC x SC, are matched pixel against "
+                        "pixel and every pixel of --dense_size is then matched inside a window around its cell's coarse "
+                        "match (eval.match_images(coarse_size=SC)).  SC divides --dense_size by a factor in [2, 8]; the "
+                        "files are the same, at --dense_size.  Default: every pixel against every pixel at --dense_size")
+    p.add_argument("--dense_radius", type=int, default=None, metavar="W",
+                   help="--dense_coarse: the window reaches W pixels of --dense_size to each side of the coarse match, "
+                        "W in [1, 16] (default: the factor + 1)")
     p.add_argument("--dense_tokens", type=str, default="all", choices=["all", "indices"],
                    help="--dense_transfer: describe a pixel by every token of embedding.pt, or by the prediction's tokens")
     p.add_argument("--dense_max_cycle", type=float, default=None,
@@ -346,7 +355,9 @@ def transfer_stage(args, ldm, controllers, embedding, indices, dataset):
 def dense_stage(args, ldm, controllers, embedding, indices, dataset):
     """``--dense_transfer SRC``: the dataset's first image is the source.  ``eval.match_images`` matches every
     pixel of every image of ``dataset`` (the source included) against it and back at ``--dense_size`` = S, over
-    every token of the embedding or (``--dense_tokens indices``) the prediction's; ``eval.transfer_labels`` carries
+    every token of the embedding or (``--dense_tokens indices``) the prediction's, with ``--dense_coarse SC`` coarse
+    to fine (every pixel against every pixel at SC, then inside a window of ``--dense_radius`` at S; a pixel whose
+    cell has no coarse match gets −1); ``eval.transfer_labels`` carries
     the source's labels over, gated by ``--dense_max_cycle`` and ``--dense_min_score`` where given.  The labels are
     ``SRC``: ``mask`` (the first item's ``mask``: foreground 0, background −1) or a saved integer tensor for the
     source (−1 = unlabelled), either nearest-resized to (S, S).  Writes ``dense_index.pt`` (M, S, S) int32,
@@ -384,7 +395,7 @@ def dense_stage(args, ldm, controllers, embedding, indices, dataset):
                              layers=args.layers, noise_level=args.noise_level, augment_degrees=args.augment_degrees,
                              augment_scale=args.augment_scale, augment_translate=args.augment_translate,
                              augmentation_iterations=args.augmentation_iterations, controllers=controllers,
-                             upscale_size=S)
+                             upscale_size=S, coarse_size=args.dense_coarse, refine_radius=args.dense_radius)
         moved = transfer_labels(match, labels, max_cycle=args.dense_max_cycle, min_score=args.dense_min_score)
         torch.save(match.index.cpu(), os.path.join(folder, "dense_index.pt"))
         torch.save(match.score.cpu(), os.path.join(folder, "dense_score.pt"))
@@ -562,6 +573,16 @@ def main(argv=None):
         parser.error("--dense_transfer belongs to --start_from_stage predict")
     if args.dense_size < 2:
         parser.error("--dense_size must be at least 2")
+    if args.dense_coarse is not None:
+        if args.dense_coarse < 1 or args.dense_size % args.dense_coarse != 0:
+            parser.error(f"--dense_coarse must divide --dense_size ({args.dense_size})")
+        if not 2 <= args.dense_size // args.dense_coarse <= 8:
+            parser.error("--dense_size / --dense_coarse must be in [2, 8]")
+    if args.dense_radius is not None:
+        if args.dense_coarse is None:
+            parser.error("--dense_radius belongs to --dense_coarse SC")
+        if not 1 <= args.dense_radius <= 16:
+            parser.error("--dense_radius must be in [1, 16]")
     if args.track and args.start_from_stage != "predict":
         parser.error("--track belongs to --start_from_stage predict")
     if args.track_size < 2:

@@ -2424,6 +2424,78 @@ def match_field(x, y):
     return index, score
 
 
+def match_refine_flops(B, n, S, f, w):
+    """Flop model of skp_match_refine: the dots of the definition, 2·n·Σ_p |W(p)| over the B images,
+    taken at its bound 2·B·n·S²·(2w + 1)² (windows clipped at the borders hold fewer pixels; the dots
+    that a cell's workgroup forms outside a pixel's window are not counted)."""
+    return 2 * B * n * S * S * (2 * w + 1) ** 2
+
+
+def match_refine_bytes(B, n, S, f, w, bx=None, by=None):
+    """Byte model of skp_match_refine: each distinct operand once (``bx``, ``by`` operands: 1 where one
+    is shared, default B) plus ``coarse``, ``index`` and ``score``.  The regions' re-reads by
+    neighbouring cells are cache traffic."""
+    bx, by = B if bx is None else bx, B if by is None else by
+    return 4 * n * S * S * (bx + by) + 4 * B * (S // f) ** 2 + 8 * B * S * S
+
+
+def match_refine(x, y, coarse, radius):
+    """The windowed refine of a coarse field (skp_match_refine): for every pixel p of ``x`` the pixel q
+    of ``y`` with the greatest cosine inside a (2·radius + 1)² window whose centre ``coarse`` gives.
+
+    ``x`` and ``y`` (B or 1, n, S, S): float32, contiguous, on one device; a leading 1 beside a B is one
+    operand shared by the B images.  ``coarse`` (B, Sc, Sc) int32 with Sc dividing S and f = S / Sc in
+    [1, 8]: per f × f cell of x's grid a cell of y's grid (row · Sc + col); the window of pixel (r, c)
+    is centred on ((m / Sc)·f + r % f, (m % Sc)·f + c % f) and clipped to the plane.  ``radius`` in
+    [1, 16].  Returns ``(index (B, S, S) int32, score (B, S, S) float32)`` with ``match_field``'s keys
+    bit for bit: the lowest usable q of the window with the greatest key and that key times 1 / |x_p|;
+    −1 and −inf where p is not usable, where its cell's prior is outside [0, Sc²) or where no q of the
+    window is usable (include/skp.h).
+    """
+    _lib.require_device(x, y, coarse)
+    for name, t in (("x", x), ("y", y)):
+        if t.dim() != 4 or t.shape[-1] != t.shape[-2]:
+            raise ValueError(f"match_refine: {name} must be (B or 1, n, S, S), got {tuple(t.shape)}")
+        if t.dtype != F32:
+            raise ValueError(f"match_refine: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"match_refine: {name} must be contiguous, got strides {t.stride()}")
+    if y.device != x.device or coarse.device != x.device:
+        raise ValueError(f"match_refine: y on {y.device}, coarse on {coarse.device}, x on {x.device}")
+    (bx, n, S, _), (by, ny, Sy, _) = x.shape, y.shape
+    if ny != n or Sy != S:
+        raise ValueError(f"match_refine: y is {ny} tokens of {Sy} x {Sy}, x is {n} tokens of {S} x {S}")
+    if coarse.dim() != 3 or coarse.shape[-1] != coarse.shape[-2] or coarse.dtype != torch.int32:
+        raise ValueError(f"match_refine: coarse must be (B, Sc, Sc) int32, got {tuple(coarse.shape)} {coarse.dtype}")
+    if not coarse.is_contiguous():
+        raise ValueError(f"match_refine: coarse must be contiguous, got strides {coarse.stride()}")
+    B, Sc = coarse.shape[0], coarse.shape[-1]
+    if bx not in (1, B):
+        raise ValueError(f"match_refine: x has {bx} images, coarse has {B}")
+    if by not in (1, B):
+        raise ValueError(f"match_refine: y has {by} images, coarse has {B}")
+    if Sc < 1 or S % Sc != 0 or not 1 <= S // Sc <= 8:
+        raise ValueError(f"match_refine: coarse is {Sc} x {Sc}, which must divide S = {S} by a factor in [1, 8]")
+    f, w = S // Sc, int(radius)
+    if not 1 <= w <= 16:
+        raise ValueError(f"match_refine: radius must be in [1, 16], got {w}")
+    dev = x.device
+    key = ("match_refine", dev, B, n, S, f, w)
+    ws = _TTA_WS.get(key)
+    if ws is None:
+        nbytes = _lib.lib().skp_match_refine_workspace(B, n, S, f, w)
+        if nbytes <= 0:
+            raise ValueError(f"match_refine: bad shape B={B}, n={n}, S={S}, f={f}, radius={w}")
+        ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    index = torch.empty(B, S, S, device=dev, dtype=torch.int32)
+    score = torch.empty(B, S, S, device=dev, dtype=F32)
+    with _timed("skp_match_refine", match_refine_bytes(B, n, S, f, w, bx, by), match_refine_flops(B, n, S, f, w)):
+        call("skp_match_refine", ptr(x), n * S * S if bx == B and B > 1 else 0, ptr(y),
+             n * S * S if by == B and B > 1 else 0, B, n, S, ptr(coarse), f, w, ptr(index), ptr(score), ptr(ws),
+             stream(dev))
+    return index, score
+
+
 # --------------------------------------------------------------------------- A20 keypoint tracks
 def track_weights(sigma, radius=None):
     """The transition table of ``track_step``: ``w[k] = exp(−k² / (2σ²))`` for k = 0 … radius, evaluated
