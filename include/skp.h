@@ -680,6 +680,61 @@ int skp_match_refine_workspace(int B, int n, int S, int f, int w);
 int skp_match_refine(const float* x, long long x_stride, const float* y, long long y_stride, int B, int n, int S,
                      const int* coarse, int f, int w, int* index, float* score, void* workspace, void* stream);
 
+/* The k best matches of a window centred on the pixel (no reference function: the search of label
+ * propagation through a video, where x is the current frame and the B images are its context frames).
+ *   x, y, x_stride, y_stride: skp_match_refine's, token-major (n, S²), a stride of 0 one operand shared
+ *   by the B images.  index (B, K, S²) int32 and score (B, K, S²) float32.
+ *   Per image, every operation fp32 and rounded on its own:
+ *   nx, ny, usable, rx, ry, dot[p,q] (the fmaf chain in token order, one accumulator per (p, q), no
+ *   split over the tokens) and key[p,q] = dot · ry[q], a NaN key counting as −inf, are skp_match_field's
+ *   word for word: a key here is bit for bit the key there.
+ *   Window: for p = (r, c), W(p) = every q = (qr, qc) of the plane with |qr − r| <= w and |qc − c| <= w:
+ *               clipped at the borders, never empty.
+ *   Slot i of pixel p: the i-th usable q of W(p) in the order (key descending, q ascending) in
+ *               index[b, i, p] and that key · rx[p] in score[b, i, p]; −1 and −inf where p is not
+ *               usable or fewer than i + 1 usable q lie in W(p).
+ *   So slot 0 is skp_match_refine with f = 1 and coarse[p] = p bit for bit, whatever K, and the first
+ *   K' slots of a K-list are the K'-list.  A result depends neither on how pixels are grouped into
+ *   workgroups, nor on the image's place in the batch, nor on what the buffers held before.  Nothing
+ *   outside the two planes is read.
+ * One launch, no atomics: one workgroup per image and 4 × 4 tile of x takes the (4 + 2w)² region of y
+ * that the tile's windows share through LDS in passes, a register-blocked fmaf kernel with the norms
+ * riding along; each pass's scaled keys go to LDS and the waves fold them into the tile's K-lists by K
+ * rounds of (key, q) maxima, pairs compared in full.  Two runs give the same bits.
+ * workspace: skp_match_topk_workspace(B, n, S, w, K) bytes (−1 on a bad shape, or at 2^31 bytes), 8-B
+ * aligned: 8 — the kernel keeps nothing in memory, no copy of y and nothing of the order of
+ * S²·(2w + 1)²; the pointer is checked and otherwise unused.
+ * Rejected before any launch: a null pointer; B, n or S below 1; n > 4096; S > 1024; w outside
+ * [1, 16]; K outside [1, 16]; a non-zero stride below n·S²; B·⌈S / 4⌉² of 2^31 or more.             */
+int skp_match_topk_workspace(int B, int n, int S, int w, int K);
+int skp_match_topk(const float* x, long long x_stride, const float* y, long long y_stride, int B, int n, int S,
+                   int w, int K, int* index, float* score, void* workspace, void* stream);
+
+/* The vote of label propagation (no reference function): per pixel the Kv best of M context frames'
+ * K-lists, weighted by a softmax of their scores, vote with their own soft labels.
+ *   index, score (M, K, S²): what skp_match_topk wrote with B = M.  An index outside [−1, S²) is
+ *   treated as −1, and so is an entry whose score is NaN (skp_match_topk writes neither).
+ *   labels (M, Cl, S²) float32: the context frames' soft labels, non-negative and finite; anything
+ *   else gives unspecified values, never a read outside the buffers.
+ *   Per pixel p: the candidates are the (j, i) with index[j, i, p] >= 0; ranks 1 … m, m <= Kv, are the
+ *   first in the order (score descending, j ascending, i ascending); (j_i, q_i, s_i) is rank i's
+ *   context, index and score.  Every operation fp32 and rounded on its own, no fma:
+ *   d_i = s_i − s_1;  a_i = d_i · inv_tau;  e_i = expf(a_i);
+ *   Z = (…(e_1 + e_2) + …) + e_m;  soft[c, p] = ((…(e_1·l_1 + e_2·l_2) + …) + e_m·l_m) / Z with
+ *   l_i = labels[j_i, c, q_i], products and sums in rank order.
+ *   expf is the HIP device library's (ocml) single-precision exp, whose documented error bound is
+ *   1 ulp; everything else is correctly rounded.  Scores that are all finite are assumed: s_1 = ±inf
+ *   gives NaN weights.
+ *   label[p] = the lowest c with the greatest soft[c, p]; confidence[p] = that value.
+ *   source (Kv, S²) int32, or null: j_i · S² + q_i at rank i, −1 from rank m on.
+ *   A pixel without a candidate gets soft 0, label −1, confidence 0.
+ * soft (Cl, S²), label (S²) int32, confidence (S²).  One launch, one thread per pixel, Kv scans of the
+ * M·K candidates; no atomics, no workspace.
+ * Rejected before any launch: a null pointer except source; M, K, S or Cl below 1; M > 64; K > 16; Kv
+ * outside [1, K]; Cl > 256; S > 1024; inv_tau not finite or not positive.                           */
+int skp_label_vote(const int* index, const float* score, int M, int K, int S, const float* labels, int Cl,
+                   float inv_tau, int Kv, float* soft, int* label, float* confidence, int* source, void* stream);
+
 /* Keypoint tracks over a sequence of frames (no reference function: visualize.create_vid takes
  * find_max_pixel frame by frame): per token the MAP path of a hidden Markov model over the pixel grid,
  * the emission a frame's TTA average, the transition a truncated Gaussian random walk.  One

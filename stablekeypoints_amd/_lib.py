@@ -116,6 +116,9 @@ _SIGS = {
     "skp_match_field": [_p, _c_ll, _c_int, _p, _c_ll, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "skp_match_refine_workspace": [_c_int, _c_int, _c_int, _c_int, _c_int],
     "skp_match_refine": [_p, _c_ll, _p, _c_ll, _c_int, _c_int, _c_int, _p, _c_int, _c_int, _p, _p, _p, _p],
+    "skp_match_topk_workspace": [_c_int, _c_int, _c_int, _c_int, _c_int],
+    "skp_match_topk": [_p, _c_ll, _p, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "skp_label_vote": [_p, _p, _c_int, _c_int, _c_int, _p, _c_int, _c_float, _c_int, _p, _p, _p, _p, _p],
     "skp_track_step_workspace": [_c_int, _c_int, _c_int],
     "skp_track_step": [_p, _p, _p, _c_int, _c_int, _p, _c_int, _p, _p, _p, _p, _p, _p],
     "skp_track_backtrace": [_p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p],

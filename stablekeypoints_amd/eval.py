@@ -988,3 +988,147 @@ def track_images(ldm, images, context, indices, device="cuda", layers=(0, 1, 2, 
         kept.append(avg.cpu())
         del avg
     return tracker.finish([f for a in kept for f in a])
+
+
+PropagatedLabels = collections.namedtuple("PropagatedLabels", ["label", "confidence", "soft"])
+
+
+class _Propagator:
+    """The frames of one sequence, one ``push`` per frame in order, then ``finish``.  Keeps on the device
+    the signatures and soft labels of frame 0 and of the last ``memory`` frames, nothing else of the
+    sequence; every frame's label and confidence (and its soft map, where asked for) wait on the host."""
+
+    def __init__(self, labels0, radius, k, tau, memory, device, keep_soft):
+        self.w, self.k, self.tau, self.memory = int(radius), int(k), float(tau), int(memory)
+        if not 1 <= self.w <= 16:
+            raise ValueError(f"radius must be in [1, 16], got {radius}")
+        if not 1 <= self.k <= 16:
+            raise ValueError(f"k must be in [1, 16], got {k}")
+        if not 0.0 < self.tau < float("inf"):
+            raise ValueError(f"tau must be positive and finite, got {tau}")
+        if self.memory < 0 or self.memory + 1 > 64:
+            raise ValueError(f"memory must be in [0, 63], got {memory}")
+        lab = torch.as_tensor(labels0)
+        if lab.dim() == 2 and not lab.is_floating_point() and lab.dtype != torch.bool:
+            if lab.shape[0] != lab.shape[1]:
+                raise ValueError(f"labels0 must be (S, S) integers or (Cl, S, S) floating point, got {tuple(lab.shape)}")
+            if lab.numel() and int(lab.min()) < -1:
+                raise ValueError("integer labels0 must be at least -1 (-1: the pixel casts no vote)")
+            Cl = max(int(lab.max()) + 1, 1) if lab.numel() else 1
+            soft = (lab[None] == torch.arange(Cl, device=lab.device)[:, None, None]).to(torch.float32)
+            label, conf = lab.to(torch.int32), (lab >= 0).to(torch.float32)
+        elif lab.dim() == 3 and lab.is_floating_point() and lab.shape[1] == lab.shape[2]:
+            soft = lab.to(torch.float32)
+            if not bool(torch.isfinite(soft).all()) or bool((soft < 0).any()):
+                raise ValueError("a soft labels0 must be finite and non-negative")
+            conf, label = soft.max(dim=0)       # the lowest class among equal maxima
+            label = label.to(torch.int32)
+        else:
+            raise ValueError(f"labels0 must be (S, S) integers or (Cl, S, S) floating point, got {tuple(lab.shape)} "
+                             f"{lab.dtype}")
+        if not 1 <= soft.shape[0] <= 256:
+            raise ValueError(f"labels0 has {soft.shape[0]} classes; at most 256")
+        self.device, self.keep_soft = torch.device(device), keep_soft
+        self.S, self.t, self.n = soft.shape[-1], 0, None
+        self.first = soft.to(self.device).contiguous()
+        self.context = []            # (frame number, signatures (n, S, S), soft labels (Cl, S, S)) in frame order
+        self.labels, self.confs, self.softs = [label.cpu()], [conf.cpu()], [soft.cpu()] if keep_soft else []
+
+    def push(self, frame):
+        a = torch.as_tensor(frame)
+        if a.dim() != 3 or tuple(a.shape[1:]) != (self.S, self.S):
+            raise ValueError(f"frame {self.t} must be (n, {self.S}, {self.S}) like labels0, got {tuple(a.shape)}")
+        a = a.to(self.device, torch.float32).contiguous()
+        if a.untyped_storage().nbytes() > a.numel() * a.element_size():
+            a = a.clone()        # a slice of a pass or of the whole video: the context must not keep that alive
+        if self.t == 0:
+            self.n = a.shape[0]
+            soft = self.first
+        else:
+            if a.shape[0] != self.n:
+                raise ValueError(f"frame {self.t} has {a.shape[0]} tokens, frame 0 had {self.n}")
+            index, score = ops.match_topk(a[None], torch.stack([c[1] for c in self.context]), self.w, self.k)
+            soft, label, conf = ops.label_vote(index, score, torch.stack([c[2] for c in self.context]), self.tau)
+            self.labels.append(label.cpu())
+            self.confs.append(conf.cpu())
+            if self.keep_soft:
+                self.softs.append(soft.cpu())
+        # frame 0 and the last `memory` frames, in frame order
+        self.context = [c for c in self.context if c[0] == 0 or c[0] > self.t - self.memory]
+        if self.t == 0 or self.memory > 0:
+            self.context.append((self.t, a, soft))
+        self.t += 1
+
+    def finish(self):
+        if self.t < 1:
+            raise ValueError("at least one frame is needed")
+        return PropagatedLabels(torch.stack(self.labels).to(self.device), torch.stack(self.confs).to(self.device),
+                                torch.stack(self.softs).to(self.device) if self.keep_soft else None)
+
+
+@torch.no_grad()
+def propagate_labels(signatures, labels0, radius=8, k=5, tau=0.07, memory=2, device="cuda", return_soft=False):
+    """A mask or part segmentation of a video's first frame carried through the remaining frames (extra:
+    the label-propagation protocol that dense self-supervised features are judged by).  For every pixel
+    of frame t the ``k`` most similar pixels within ``radius`` of it in each context frame are found
+    (``ops.match_topk``, the signatures' cosines); the ``k`` best of them all, weighted by
+    ``softmax(cosine / tau)``, vote with their own soft labels (``ops.label_vote``).  The context of
+    frame t is frame 0 and the last ``memory`` frames, distinct and in frame order; frame 0 keeps its
+    given labels, and each later frame's soft output is its label map for the frames after it.
+
+    ``signatures`` is a (T, n, S, S) tensor or any iterable of (n, S, S) frames in frame order: what
+    ``predict_keypoints(return_maps=True)`` returns for all tokens.  Frames are uploaded to ``device`` one
+    at a time (a tensor on a HIP device stays where it is); only the context's signatures and soft
+    labels stay there.  ``labels0`` is (S, S) integers — class c >= 0 becomes a one-hot plane, and a −1
+    is not background: it becomes an all-zero column, so that pixel casts no vote — or a (Cl, S, S)
+    soft map, finite and non-negative.  ``radius`` and ``k`` in [1, 16], ``memory`` in [0, 63].
+
+    Returns ``PropagatedLabels(label, confidence, soft)``: ``label`` (T, S, S) int32 the lowest class with
+    the greatest soft value (−1 where no context pixel could be matched; frame 0: the given integers, or
+    the soft map's argmax), ``confidence`` (T, S, S) float32 that value, ``soft`` (T, Cl, S, S) with
+    ``return_soft``, else None.  The defaults are DINO's protocol (radius 12, k 5, temperature 0.07 at
+    stride-8 features of 480p video) scaled to 128²; their suitability for these signatures has not
+    been measured, nor has the quality of propagated labels on real video.
+    """
+    if torch.is_tensor(signatures):
+        if signatures.dim() != 4:
+            raise ValueError(f"signatures must be (T, n, S, S) or an iterable of (n, S, S) frames, got "
+                             f"{tuple(signatures.shape)}")
+        if signatures.is_cuda:
+            device = signatures.device
+    prop = _Propagator(labels0, radius, k, tau, memory, device, return_soft)
+    for frame in signatures:
+        prop.push(frame)
+    return prop.finish()
+
+
+@torch.no_grad()
+def propagate_images(ldm, images, context, labels0, indices=None, device="cuda", layers=(0, 1, 2, 3, 4, 5),
+                     noise_level=-1, augment_degrees=30, augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1),
+                     augmentation_iterations=20, controllers=None, upscale_size=128, image_batch=None, radius=8, k=5,
+                     tau=0.07, memory=2, return_soft=False):
+    """``propagate_labels`` of the frames of a video: ``images`` (T, 3, H, W) in [0, 1], in frame order,
+    ``labels0`` frame 0's labels at ``upscale_size``, ``indices`` the tokens that describe a pixel
+    (default every token of ``context``).
+
+    The thetas are drawn and the passes captured as ``predict_keypoints`` does (``_tta_passes``); each
+    pass's averages, from ``ops.tta_reduce(return_avg=True)``, are fed to the propagation frame by frame
+    as they come, so no more than one pass of captured maps, one pass of averages and the context is on
+    the device at a time.  The result is what ``propagate_labels`` gives on
+    ``predict_keypoints(..., return_maps=True)``'s maps from the same seed, bit for bit.  Single process
+    only: under a process group of more than one rank it raises.
+    """
+    C, S = int(augmentation_iterations), int(upscale_size)
+    indices = _tokens_of(indices, context, C, S, "propagate with")
+    prop = _Propagator(labels0, radius, k, tau, memory, device, return_soft)
+    if prop.S != S:
+        raise ValueError(f"labels0 is {prop.S} x {prop.S}, upscale_size is {S}")
+    for _, nb, maps, th_inv in _tta_passes("propagate_images", ldm, images, context, indices, device, layers,
+                                           noise_level, augment_degrees, augment_scale, augment_translate, C,
+                                           controllers, S, image_batch):
+        _, avg = ops.tta_reduce(maps, th_inv, return_avg=True)
+        del maps
+        for b in range(nb):
+            prop.push(avg[b])
+        del avg
+    return prop.finish()

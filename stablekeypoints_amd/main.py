@@ -26,7 +26,10 @@ a field at SC refined inside windows at ``--dense_size``: ``dense_index.pt``, ``
 ``dense_fg_iou.pt`` where the dataset has foreground masks, and with ``--visualize`` ``dense.png``).  With ``--track`` the
 dataset's items in index order are the frames of a video and it also writes one track per token (``eval.track_images`` at
 ``--track_size``, ``--track_sigma`` and ``--track_radius``: ``tracked_keypoints.pt``, ``track_support.pt``,
-``tracked_keypoints.csv``, and with ``--visualize`` ``track.png``).  With ``--visualize``,
+``tracked_keypoints.csv``, and with ``--visualize`` ``track.png``).  With ``--propagate SRC`` the items are frames likewise and
+the first frame's labels are carried through them (``eval.propagate_images`` at ``--propagate_size`` with ``--propagate_radius``,
+``--propagate_k``, ``--propagate_tau`` and ``--propagate_memory``: ``propagated_labels.pt``, ``propagated_confidence.pt``,
+``propagated_fg_iou.pt`` where the dataset has foreground masks, and with ``--visualize`` ``propagate.png``).  With ``--visualize``,
 ``visualize_attn_maps`` writes its sheets after find_indices and again, with the regressor, once
 that is fitted (``main.py:271-292``, ``:370-391``); the reference calls both unconditionally, here
 they are opt-in so that a run without the flag does what it always did.  Multi-GPU: like the
@@ -160,6 +163,22 @@ def build_parser():
     p.add_argument("--track_radius", type=int, default=None,
                    help="--track: the longest step per frame and axis, 1 to 32 pixels (default ceil(3 sigma), clipped)")
     p.add_argument("--track_size", type=int, default=128, help="--track: side S of the averages that are tracked")
+    p.add_argument("--propagate", type=str, default=None, metavar="SRC",
+                   help="--start_from_stage predict: the dataset's items in index order are the frames of a video; also "
+                        "carry the first frame's labels through them: every pixel's k most similar pixels in a window of "
+                        "the first and the last few frames vote (propagated_labels.pt (M, S, S) int32, "
+                        "propagated_confidence.pt (M, S, S), and propagated_fg_iou.pt where the dataset has foreground "
+                        "masks).  SRC: 'mask' (the first item's mask: foreground 1, background 0) or a saved (h, w) "
+                        "integer tensor for the first frame, -1 = casts no vote, nearest-resized to --propagate_size")
+    p.add_argument("--propagate_size", type=int, default=128, help="--propagate: side S of the averages that are matched")
+    p.add_argument("--propagate_radius", type=int, default=8,
+                   help="--propagate: the window reaches this many pixels of --propagate_size to each side, 1 to 16")
+    p.add_argument("--propagate_k", type=int, default=5, help="--propagate: the matches that vote per pixel, 1 to 16")
+    p.add_argument("--propagate_tau", type=float, default=0.07, help="--propagate: the temperature of the votes' softmax")
+    p.add_argument("--propagate_memory", type=int, default=2,
+                   help="--propagate: the context is the first frame and this many of the last frames, 0 to 63")
+    p.add_argument("--propagate_tokens", type=str, default="all", choices=["all", "indices"],
+                   help="--propagate: describe a pixel by every token of embedding.pt, or by the prediction's tokens")
     return p
 
 
@@ -451,6 +470,71 @@ def track_stage(args, ldm, controllers, embedding, indices, dataset):
               f"{os.path.join(folder, 'tracked_keypoints.pt')}", flush=True)
 
 
+def propagate_stage(args, ldm, controllers, embedding, indices, dataset):
+    """``--propagate SRC``: the dataset's items in index order are the frames of a video.  ``eval.propagate_images``
+    carries the first frame's labels through them at ``--propagate_size`` = S over every token of the embedding or
+    (``--propagate_tokens indices``) the prediction's, with ``--propagate_radius``, ``--propagate_k``, ``--propagate_tau``
+    and ``--propagate_memory``.  The labels are ``SRC``: ``mask`` (the first item's ``mask``: foreground 1, background 0) or
+    a saved integer tensor for the first frame (−1 = the pixel casts no vote), either nearest-resized to (S, S).
+    Writes ``propagated_labels.pt`` (M, S, S) int32 and ``propagated_confidence.pt`` (M, S, S) float32; where the
+    dataset's items carry ``mask`` also ``propagated_fg_iou.pt`` (M,) float64, ``eval.foreground_iou`` of the pixels whose
+    label is at least 1 (with ``mask``: the foreground), and prints its mean over the later frames.  With ``--visualize``
+    ``propagate.png``, tinted as ``parts.png`` is.  The CPU and device RNG states are what they were on entry when it
+    returns, so the prediction that follows draws what a plain predict run draws."""
+    from . import ops
+    from .eval import foreground_iou, propagate_images
+    folder, S, M = args.save_folder, int(args.propagate_size), len(dataset)
+    if M < 1:
+        raise ValueError("--propagate: the dataset is empty")
+    with _rng_restored(args.device):
+        items = [dataset[i] for i in range(M)]
+        images = torch.stack([torch.as_tensor(it["img"]) for it in items])
+        have_masks = all("mask" in it for it in items)
+        if args.propagate == "mask":
+            if "mask" not in items[0]:
+                raise ValueError("--propagate mask: the dataset's items carry no mask; give a file of labels")
+            mask = torch.as_tensor(items[0]["mask"], dtype=torch.float32)
+            mask = mask[..., 0] if mask.dim() == 3 and mask.shape[-1] == 1 else mask
+            labels = torch.where(mask > 0.5, 1, 0)
+        else:
+            labels = torch.as_tensor(torch.load(args.propagate, weights_only=True))
+            if labels.dim() != 2 or labels.is_floating_point() or labels.dtype == torch.bool:
+                raise ValueError(f"--propagate: the file must hold an (h, w) integer tensor, got "
+                                 f"{tuple(labels.shape)} {labels.dtype}")
+        if tuple(labels.shape) != (S, S):
+            labels = torch.nn.functional.interpolate(labels[None, None].to(torch.float32), size=(S, S),
+                                                     mode="nearest")[0, 0]
+        labels = labels.to(torch.int64)
+        got = propagate_images(ldm, images, embedding, labels,
+                               None if args.propagate_tokens == "all" else indices.cpu(), device=args.device,
+                               layers=args.layers, noise_level=args.noise_level, augment_degrees=args.augment_degrees,
+                               augment_scale=args.augment_scale, augment_translate=args.augment_translate,
+                               augmentation_iterations=args.augmentation_iterations, controllers=controllers,
+                               upscale_size=S, radius=args.propagate_radius, k=args.propagate_k, tau=args.propagate_tau,
+                               memory=args.propagate_memory)
+        torch.save(got.label.cpu(), os.path.join(folder, "propagated_labels.pt"))
+        torch.save(got.confidence.cpu(), os.path.join(folder, "propagated_confidence.pt"))
+        if have_masks:
+            masks = torch.stack([torch.as_tensor(it["mask"], dtype=torch.float32) for it in items])
+            iou = foreground_iou(torch.where(got.label >= 1, 0, -1), masks).cpu()
+            torch.save(iou, os.path.join(folder, "propagated_fg_iou.pt"))
+            rest = iou[1:]
+            mean = float(rest.mean()) if rest.numel() else float("nan")
+            print(f"propagate: mean foreground IoU {mean:.4f} over {rest.numel()} later frames", flush=True)
+        if args.visualize:
+            m = min(12, M)
+            shown = images[:m].to(args.device, torch.float32)
+            label = torch.nn.functional.interpolate(got.label[:m, None].float(), size=tuple(images.shape[-2:]),
+                                                    mode="nearest")[:, 0].long()
+            colors = ops.default_colors(int(got.label.max().clamp_min(0)) + 1).to(args.device)
+            tint = (colors.float() / 255.0)[label.clamp_min(0)].permute(0, 3, 1, 2)
+            shown = torch.where((label >= 0)[:, None], 0.5 * shown + 0.5 * tint, shown)
+            _save_row_sheet(os.path.join(folder, "propagate.png"), shown, torch.zeros(m, 0, 2, device=args.device),
+                            args.device)
+        print(f"propagate: {M} frames at {S}, radius {args.propagate_radius}, k {args.propagate_k} -> "
+              f"{os.path.join(folder, 'propagated_labels.pt')}", flush=True)
+
+
 def predict_stage(args, ldm, controllers, batch=4):
     """``--start_from_stage predict``: the keypoints of every image of the dataset (built as
     ``evaluate`` builds it: ``split="test"``, the whole folder for ``custom``), in index order, from
@@ -494,6 +578,8 @@ def predict_stage(args, ldm, controllers, batch=4):
         dense_stage(args, ldm, controllers, embedding, indices, dataset)
     if args.track:
         track_stage(args, ldm, controllers, embedding, indices, dataset)
+    if args.propagate is not None:
+        propagate_stage(args, ldm, controllers, embedding, indices, dataset)
     names = _image_names(dataset)
     k = int(args.num_subjects)
     kps, regs, scos, refs, pks, vals = [], [], [], [], [], []
@@ -591,6 +677,20 @@ def main(argv=None):
         parser.error("--track_sigma must be positive and finite")
     if args.track_radius is not None and not 1 <= args.track_radius <= 32:
         parser.error("--track_radius must be in [1, 32]")
+    if args.propagate is not None and args.start_from_stage != "predict":
+        parser.error("--propagate belongs to --start_from_stage predict")
+    if args.propagate_size < 2:
+        parser.error("--propagate_size must be at least 2")
+    if args.propagate_size > 1024:
+        parser.error("--propagate_size must be at most 1024")
+    if not 1 <= args.propagate_radius <= 16:
+        parser.error("--propagate_radius must be in [1, 16]")
+    if not 1 <= args.propagate_k <= 16:
+        parser.error("--propagate_k must be in [1, 16]")
+    if not 0.0 < args.propagate_tau < float("inf"):
+        parser.error("--propagate_tau must be positive and finite")
+    if not 0 <= args.propagate_memory <= 63:
+        parser.error("--propagate_memory must be in [0, 63]")
     from .launch import launcher_env, spawn_ranks
     # torch.cuda.device_count() does not initialise HIP on this image, so the ranks can still start
     n = ranks_to_start(args, torch.cuda.device_count(), launcher_env())

@@ -2496,6 +2496,127 @@ def match_refine(x, y, coarse, radius):
     return index, score
 
 
+# --------------------------------------------------------------------------- A21 label propagation
+def match_topk_flops(B, n, S, w):
+    """Flop model of skp_match_topk: the dots of the definition at their bound, 2·B·n·S²·(2w + 1)²
+    (windows clipped at the borders hold fewer pixels; the dots that a tile's workgroup forms outside a
+    pixel's window, and the selection, are not counted)."""
+    return 2 * B * n * S * S * (2 * w + 1) ** 2
+
+
+def match_topk_bytes(B, n, S, w, k, bx=None, by=None):
+    """Byte model of skp_match_topk: each distinct operand once (``bx``, ``by`` operands: 1 where one is
+    shared, default B) plus the k slots of ``index`` and ``score``.  The regions' re-reads by
+    neighbouring tiles are cache traffic."""
+    bx, by = B if bx is None else bx, B if by is None else by
+    return 4 * n * S * S * (bx + by) + 8 * B * k * S * S
+
+
+def match_topk(x, y, radius, k):
+    """The k best matches of a window centred on the pixel (skp_match_topk): for every pixel p of ``x``
+    the ``k`` pixels q of ``y`` with the greatest cosine among those within ``radius`` of p on each axis.
+
+    ``x`` and ``y`` (B or 1, n, S, S): float32, contiguous, on one device; a leading 1 beside a B is one
+    operand shared by the B images (in label propagation x is the current frame and y its context
+    frames).  ``radius`` in [1, 16], ``k`` in [1, 16].  Returns ``(index (B, k, S, S) int32, score
+    (B, k, S, S) float32)`` with ``match_field``'s keys bit for bit: slot i holds the i-th usable q of the
+    window in the order (key descending, q ascending) and that key times 1 / |x_p|; −1 and −inf where
+    p is not usable or the window holds fewer usable pixels (include/skp.h).  Slot 0 is
+    ``match_refine`` with an identity prior.
+    """
+    _lib.require_device(x, y)
+    for name, t in (("x", x), ("y", y)):
+        if t.dim() != 4 or t.shape[-1] != t.shape[-2]:
+            raise ValueError(f"match_topk: {name} must be (B or 1, n, S, S), got {tuple(t.shape)}")
+        if t.dtype != F32:
+            raise ValueError(f"match_topk: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"match_topk: {name} must be contiguous, got strides {t.stride()}")
+    if y.device != x.device:
+        raise ValueError(f"match_topk: y on {y.device}, x on {x.device}")
+    (bx, n, S, _), (by, ny, Sy, _) = x.shape, y.shape
+    if ny != n or Sy != S:
+        raise ValueError(f"match_topk: y is {ny} tokens of {Sy} x {Sy}, x is {n} tokens of {S} x {S}")
+    B = max(bx, by)
+    if bx not in (1, B):
+        raise ValueError(f"match_topk: x has {bx} images, y has {by}")
+    if by not in (1, B):
+        raise ValueError(f"match_topk: y has {by} images, x has {bx}")
+    w, K = int(radius), int(k)
+    if not 1 <= w <= 16:
+        raise ValueError(f"match_topk: radius must be in [1, 16], got {w}")
+    if not 1 <= K <= 16:
+        raise ValueError(f"match_topk: k must be in [1, 16], got {K}")
+    dev = x.device
+    key = ("match_topk", dev, B, n, S, w, K)
+    ws = _TTA_WS.get(key)
+    if ws is None:
+        nbytes = _lib.lib().skp_match_topk_workspace(B, n, S, w, K)
+        if nbytes <= 0:
+            raise ValueError(f"match_topk: bad shape B={B}, n={n}, S={S}, radius={w}, k={K}")
+        ws = _TTA_WS[key] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    index = torch.empty(B, K, S, S, device=dev, dtype=torch.int32)
+    score = torch.empty(B, K, S, S, device=dev, dtype=F32)
+    with _timed("skp_match_topk", match_topk_bytes(B, n, S, w, K, bx, by), match_topk_flops(B, n, S, w)):
+        call("skp_match_topk", ptr(x), n * S * S if bx == B and B > 1 else 0, ptr(y),
+             n * S * S if by == B and B > 1 else 0, B, n, S, w, K, ptr(index), ptr(score), ptr(ws), stream(dev))
+    return index, score
+
+
+def label_vote_bytes(M, K, S, Cl, kv, source=False):
+    """Byte model of skp_label_vote: the M·K slots of ``index`` and ``score`` once (the kv scans re-read
+    them from the caches), kv gathered labels per class, and ``soft``, ``label``, ``confidence`` and
+    ``source`` written."""
+    return S * S * (8 * M * K + 4 * Cl * kv + 4 * Cl + 8 + (4 * kv if source else 0))
+
+
+def label_vote(index, score, labels, tau, k=None, return_source=False):
+    """The vote of label propagation (skp_label_vote): per pixel the ``k`` best entries of M context
+    frames' match lists, weighted by ``softmax(score / tau)``, vote with their own soft labels.
+
+    ``index`` (M, K, S, S) int32 and ``score`` (M, K, S, S) float32: ``match_topk``'s with B = M <= 64.
+    ``labels`` (M, Cl, S, S) float32, non-negative and finite, Cl <= 256: the context frames' soft
+    labels.  ``tau`` positive; the kernel takes ``1 / tau`` rounded once to float32.  ``k`` in [1, K],
+    default K.  Returns ``(soft (Cl, S, S) float32, label (S, S) int32, confidence (S, S) float32)``
+    and with ``return_source`` also ``source`` (k, S, S) int32, j · S² + q of each rank or −1:
+    ``label`` is the lowest class with the greatest ``soft`` value and ``confidence`` that value; a pixel
+    without a candidate gets 0, −1, 0 (include/skp.h has the order of every operation).
+    """
+    _lib.require_device(index, score, labels)
+    if index.dim() != 4 or index.shape[-1] != index.shape[-2] or index.dtype != torch.int32:
+        raise ValueError(f"label_vote: index must be (M, K, S, S) int32, got {tuple(index.shape)} {index.dtype}")
+    if tuple(score.shape) != tuple(index.shape) or score.dtype != F32:
+        raise ValueError(f"label_vote: score must be {tuple(index.shape)} float32, got {tuple(score.shape)} {score.dtype}")
+    M, K, S, _ = index.shape
+    if labels.dim() != 4 or labels.shape[0] != M or tuple(labels.shape[2:]) != (S, S) or labels.dtype != F32:
+        raise ValueError(f"label_vote: labels must be ({M}, Cl, {S}, {S}) float32, got {tuple(labels.shape)} {labels.dtype}")
+    for name, t in (("index", index), ("score", score), ("labels", labels)):
+        if not t.is_contiguous():
+            raise ValueError(f"label_vote: {name} must be contiguous, got strides {t.stride()}")
+    if score.device != index.device or labels.device != index.device:
+        raise ValueError(f"label_vote: score on {score.device}, labels on {labels.device}, index on {index.device}")
+    Cl = labels.shape[1]
+    if not 1 <= M <= 64 or not 1 <= K <= 16 or not 1 <= Cl <= 256 or not 1 <= S <= 1024:
+        raise ValueError(f"label_vote: M in [1, 64], K in [1, 16], Cl in [1, 256] and S in [1, 1024], got M={M}, K={K}, "
+                         f"Cl={Cl}, S={S}")
+    kv = K if k is None else int(k)
+    if not 1 <= kv <= K:
+        raise ValueError(f"label_vote: k must be in [1, {K}], got {kv}")
+    t = float(tau)
+    inv_tau = float(torch.tensor(1.0 / t if t > 0.0 else float("nan"), dtype=torch.float64).to(F32))
+    if not 0.0 < inv_tau < float("inf"):
+        raise ValueError(f"label_vote: tau must be positive with a finite float32 inverse, got {tau}")
+    dev = index.device
+    soft = torch.empty(Cl, S, S, device=dev, dtype=F32)
+    label = torch.empty(S, S, device=dev, dtype=torch.int32)
+    conf = torch.empty(S, S, device=dev, dtype=F32)
+    source = torch.empty(kv, S, S, device=dev, dtype=torch.int32) if return_source else None
+    with _timed("skp_label_vote", label_vote_bytes(M, K, S, Cl, kv, return_source)):
+        call("skp_label_vote", ptr(index), ptr(score), M, K, S, ptr(labels), Cl, inv_tau, kv, ptr(soft), ptr(label),
+             ptr(conf), ptr(source), stream(dev))
+    return (soft, label, conf, source) if return_source else (soft, label, conf)
+
+
 # --------------------------------------------------------------------------- A20 keypoint tracks
 def track_weights(sigma, radius=None):
     """The transition table of ``track_step``: ``w[k] = exp(−k² / (2σ²))`` for k = 0 … radius, evaluated
