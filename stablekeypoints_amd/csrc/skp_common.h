@@ -181,6 +181,10 @@ struct Taps2 {
   float w0, w1;
 };
 __device__ __forceinline__ Taps2 bilinear_taps(int dst, int n_in, int n_out) {
+  // the product rounded, then the difference, as torch-CPU and the oracle round it: contracted into
+  // one fused multiply-add, src (and with it a tap weight) moves by an ulp of src, 1.9e-6 from src = 16
+  // on.  (__fmul_rn / __fsub_rn are plain operators here and contract like them.)
+#pragma clang fp contract(off)
   const float scale = (float)n_in / (float)n_out;
   float src = scale * ((float)dst + 0.5f) - 0.5f;
   src = src < 0.0f ? 0.0f : src;

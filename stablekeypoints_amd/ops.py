@@ -628,6 +628,13 @@ def argmax_index(maps):
     return idx
 
 
+def _square(name, t):
+    """Sharpening and the KL target are defined for square maps only (the reference builds an h×h
+    target for an (h, w) map and fails on the mismatch); the kernels mix /w and ·h."""
+    if t.shape[-2] != t.shape[-1]:
+        raise ValueError(f"{name} must hold square maps (h == w), got {tuple(t.shape)}")
+
+
 def _radius2(h):
     r = 0.05 * h
     return float(r ** 2)
@@ -682,6 +689,7 @@ def gaussian_circles(pos, size, sigma):
 # --------------------------------------------------------------------------- A8-A10 selection
 def find_top_k_gaussian(maps, top_k, sigma=3, epsilon=1e-5, num_subjects=1, return_kl=False):
     _lib.require_device(maps)
+    _square("maps", maps)
     maps = _c(maps)
     T, h, w = maps.shape
     top_k = min(int(top_k), T)   # argsort(kl)[:top_k] (ptp_utils.py:110): at most T candidates
@@ -698,6 +706,7 @@ def find_top_k_gaussian_batch(maps, top_k, sigma=3, epsilon=1e-5, num_subjects=1
     """find_top_k_gaussian of every image of a (nb, T, h, w) stack in one launch each for the KL
     ranking and the sort: (nb, top_k) int64, row b = find_top_k_gaussian(maps[b], ...)."""
     _lib.require_device(maps)
+    _square("maps", maps)
     maps = _c(maps)
     nb, T, h, w = maps.shape
     top_k = min(int(top_k), T)
@@ -852,6 +861,7 @@ class SharpeningLoss(torch.autograd.Function):
 
 def sharpening_loss(A, sigma=1.0, num_subjects=1):
     _lib.require_device(A)
+    _square("A", A)
     return SharpeningLoss.apply(A, float(sigma), int(num_subjects))
 
 
@@ -887,6 +897,7 @@ class SharpeningLossBatch(torch.autograd.Function):
 def sharpening_loss_batch(A, nb, sigma=1.0, num_subjects=1):
     """(nb,) sharpening losses of nb images whose T selected rows each are stacked in A (nb·T, h, w)."""
     _lib.require_device(A)
+    _square("A", A)
     if A.shape[0] % nb:
         raise ValueError(f"{A.shape[0]} rows for {nb} images")
     return SharpeningLossBatch.apply(A, int(nb), float(sigma), int(num_subjects))
